@@ -9,6 +9,17 @@ W untimed warmup steps, then EXACTLY K timed steps bracketed by
 barrier + torch.cuda.synchronize on both sides; elapsed = MAX over ranks;
 rank 0 prints ONE JSON line. Synthetic data (random tokens of the config's
 shape), random-init weights, full optimizer step inside the timed region.
+
+A plain run does only that: set up, warm up, time the K steps, print the
+result line. Options on top of it:
+  --dump-outputs DIR  after the timed steps, rank 0 writes what the last
+                      timed train_step produced as DIR/<name>.npy (float32):
+                      loss, ntokens, losses (every timed step), and a fixed
+                      seeded sample of the flat parameter and gradient
+                      buffers. Inputs and init are seeded, so the same
+                      arguments give comparable files from build to build.
+  --full              reserved for extra measurements beyond the headline
+                      figure; there are none at present, so it is a no-op.
 """
 from __future__ import annotations
 
@@ -19,6 +30,7 @@ import sys
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 
 REPO = Path(__file__).resolve().parent
@@ -31,6 +43,32 @@ from mlx_cuda_distributed_pretraining_amd.parallel.dist import (  # noqa: E402
 )
 
 BASELINE_TOKS_PER_SEC = 25000.0  # reference: 1.3B @ ~25K tok/s on 2xA100-40GB
+DUMP_SAMPLE = 1 << 20  # elements sampled from each flat buffer (4 MB as fp32)
+
+
+def _sample_flat(flat: torch.Tensor, n: int = DUMP_SAMPLE) -> np.ndarray:
+    """Fixed, seeded sample of a flat buffer (all of it when small enough)."""
+    flat = flat.detach().reshape(-1)
+    if flat.numel() > n:
+        g = torch.Generator().manual_seed(1234)
+        idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(out_dir: str, trainer: Trainer, losses: list, ntok) -> None:
+    """Write the last timed step's results as <out_dir>/<name>.npy (float32)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {
+        "loss": losses[-1].detach().float().reshape(1).cpu().numpy(),
+        "ntokens": torch.as_tensor(ntok).detach().float().reshape(1).cpu().numpy(),
+        "losses": torch.stack([l.detach().float().reshape(()) for l in losses]).cpu().numpy(),
+        "param_sample": _sample_flat(trainer.flat_space.flat_param),
+        "grad_sample": _sample_flat(trainer.flat_space.flat_grad),
+    }
+    for name, arr in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def main() -> None:
@@ -41,6 +79,10 @@ def main() -> None:
     p.add_argument("--config", type=str, default=None)
     p.add_argument("--batch-size", type=int, default=None)
     p.add_argument("--seq-len", type=int, default=None)
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write the last timed step's outputs as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the extra measurements (none at present)")
     args = p.parse_args()
 
     on_gpu = torch.cuda.is_available()
@@ -83,10 +125,12 @@ def main() -> None:
     if on_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    last_loss = None
+    losses = []  # per-step loss tensors, kept only for --dump-outputs
+    last_loss = last_ntok = None
     for i in range(args.warmup, args.warmup + args.steps):
-        loss, _ = trainer.train_step(i)
-        last_loss = loss
+        last_loss, last_ntok = trainer.train_step(i)
+        if args.dump_outputs:
+            losses.append(last_loss)
     if on_gpu:
         torch.cuda.synchronize()
     barrier()
@@ -104,6 +148,9 @@ def main() -> None:
     value = tokens_per_step * args.steps / elapsed_s
     ms_per_step = 1000.0 * elapsed_s / args.steps
     model_name = "Llama-1B" if "1b" in Path(cfg_path).stem else Path(cfg_path).stem
+
+    if args.dump_outputs and rank == 0 and losses:
+        dump_outputs(args.dump_outputs, trainer, losses, last_ntok)
 
     if rank == 0:
         result = {

@@ -96,4 +96,18 @@ __device__ __forceinline__ float block_reduce_max(float v, float* lds_scratch) {
   return r;
 }
 
+// Second stage of a two-stage sum: one block adds the n per-block partials in
+// a fixed order, so the result is bit-identical from run to run (a float
+// atomicAdd per block is not: the order of arrival changes the rounding).
+// Launch with <<<1, BLOCK>>>.
+template <int BLOCK>
+__global__ void reduce_partials_kernel(const float* __restrict__ partials, int n,
+                                       float* __restrict__ out) {
+  __shared__ float scratch[BLOCK / WAVE];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n; i += BLOCK) acc += partials[i];
+  acc = block_reduce_sum<BLOCK>(acc, scratch);
+  if (threadIdx.x == 0) *out = acc;
+}
+
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }

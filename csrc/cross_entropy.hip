@@ -11,9 +11,13 @@ namespace {
 
 template <typename T, int BLOCK>
 __global__ void ce_fwd_kernel(const T* __restrict__ logits, const long* __restrict__ targets,
-                              float* __restrict__ loss_sum, long* __restrict__ ntok,
+                              float* __restrict__ loss_partials, long* __restrict__ ntok,
                               float* __restrict__ lse_out, long rows, int V, long ignore_index) {
   __shared__ float scratch[BLOCK / WAVE];
+  // thread 0 adds this block's rows in row order; reduce_partials_kernel then
+  // adds the per-block partials in a fixed order, so the loss is the same
+  // every run (the integer token count is order-independent as an atomic)
+  float block_loss = 0.f;
   for (long row = blockIdx.x; row < rows; row += gridDim.x) {
     const T* lr = logits + row * (long)V;
     // pass 1: max
@@ -51,11 +55,12 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits, const long* __restri
       lse_out[row] = lse;
       const long t = targets[row];
       if (t != ignore_index) {
-        atomicAdd(loss_sum, lse - to_f32(lr[t]));
+        block_loss += lse - to_f32(lr[t]);
         atomicAdd(reinterpret_cast<unsigned long long*>(ntok), 1ull);
       }
     }
   }
+  if (threadIdx.x == 0) loss_partials[blockIdx.x] = block_loss;
 }
 
 template <typename T>
@@ -178,23 +183,26 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets, long ignor
   TORCH_CHECK(targets.scalar_type() == at::kLong);
   const long rows = logits.size(0);
   const int V = logits.size(1);
-  auto loss_sum = at::zeros({}, logits.options().dtype(at::kFloat));
+  auto loss_sum = at::empty({}, logits.options().dtype(at::kFloat));
   auto ntok = at::zeros({}, logits.options().dtype(at::kLong));
   auto lse = at::empty({rows}, logits.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentHIPStream();
   constexpr int BLOCK = 256;
   const long grid = std::min<long>(rows, 4096);
+  auto partials = at::empty({grid}, logits.options().dtype(at::kFloat));
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, logits.scalar_type(), "ce_fwd", [&] {
     using T = std::conditional_t<std::is_same_v<scalar_t, at::BFloat16>, __hip_bfloat16, float>;
     if constexpr (std::is_same_v<scalar_t, at::BFloat16> || std::is_same_v<scalar_t, float>) {
       ce_fwd_kernel<T, BLOCK><<<grid, BLOCK, 0, stream>>>(
           reinterpret_cast<const T*>(logits.data_ptr()), targets.data_ptr<long>(),
-          loss_sum.data_ptr<float>(), ntok.data_ptr<long>(), lse.data_ptr<float>(),
+          partials.data_ptr<float>(), ntok.data_ptr<long>(), lse.data_ptr<float>(),
           rows, V, ignore_index);
     } else {
       TORCH_CHECK(false, "ce: unsupported dtype");
     }
   });
+  reduce_partials_kernel<256><<<1, 256, 0, stream>>>(
+      partials.data_ptr<float>(), (int)grid, loss_sum.data_ptr<float>());
   return {loss_sum, ntok, lse};
 }
 

@@ -10,8 +10,10 @@
 namespace {
 
 // ---------------- sum of squares ----------------
+// Stage 1: one partial per block (plain store); reduce_partials_kernel adds
+// them in a fixed order, so the clip coefficient is the same every run.
 template <typename T>
-__global__ void sumsq_kernel(const T* __restrict__ g, float* __restrict__ out, long n) {
+__global__ void sumsq_kernel(const T* __restrict__ g, float* __restrict__ partials, long n) {
   float acc = 0.f;
   if constexpr (sizeof(T) == 2) {
     const long nv = n / 8;
@@ -30,7 +32,7 @@ __global__ void sumsq_kernel(const T* __restrict__ g, float* __restrict__ out, l
   }
   __shared__ float scratch[256 / WAVE];
   acc = block_reduce_sum<256>(acc, scratch);
-  if (threadIdx.x == 0) atomicAdd(out, acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
 __device__ __forceinline__ float clip_coef(const float* sumsq, float max_norm) {
@@ -115,17 +117,20 @@ void dispatch_pg(at::Tensor& param, at::Tensor& grad, F&& f) {
 
 at::Tensor sumsq(at::Tensor g) {
   TORCH_CHECK(g.is_cuda() && g.is_contiguous());
-  auto out = at::zeros({}, g.options().dtype(at::kFloat));
+  auto out = at::empty({}, g.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentHIPStream();
   const long n = g.numel();
   const int block = 256;
   const long grid = std::min<long>(cdiv(n / 8 + 1, block), 2048);
+  auto partials = at::empty({grid}, g.options().dtype(at::kFloat));
   if (g.scalar_type() == at::kBFloat16)
     sumsq_kernel<__hip_bfloat16><<<grid, block, 0, stream>>>(
-        reinterpret_cast<const __hip_bfloat16*>(g.data_ptr()), out.data_ptr<float>(), n);
+        reinterpret_cast<const __hip_bfloat16*>(g.data_ptr()), partials.data_ptr<float>(), n);
   else
     sumsq_kernel<float><<<grid, block, 0, stream>>>(
-        g.data_ptr<float>(), out.data_ptr<float>(), n);
+        g.data_ptr<float>(), partials.data_ptr<float>(), n);
+  reduce_partials_kernel<256><<<1, 256, 0, stream>>>(
+      partials.data_ptr<float>(), (int)grid, out.data_ptr<float>());
   return out;
 }
 

@@ -141,6 +141,46 @@ def test_sumsq_and_adamw_gpu(ext):
     assert torch.allclose(param.float(), master, atol=1e-2, rtol=1e-2)
 
 
+def test_loss_and_sumsq_reductions_bit_repeatable(ext):
+    """The CE loss sum and the grad sum-of-squares are two-stage fixed-order
+    reductions: repeated calls on the same input agree bit for bit (a float
+    atomic per block would not), at sizes past the grid caps (4096 row blocks,
+    2048 sumsq blocks) so blocks loop, with an odd tail.
+
+    Tolerances vs the fp64 reference: an fp32 sum of n same-sign terms errs
+    by at most ~n * 2^-24 relative. sumsq: ~80 terms per thread plus a
+    ~20-level tree, < 1e-5; bound 1e-4 (one dropped block of 2048 is 5e-4).
+    CE sum: 2 rows per block, 16 partials per thread, a 14-level tree,
+    < 2e-6; each row's lse carries the fast exp/log error (argument scaling
+    of |x| < 8 at 2^-24, ~5e-7 absolute on values near 6, 1e-7 relative);
+    bound 1e-5 (one dropped row of ~4286 counted is 2.3e-4)."""
+    from mlx_cuda_distributed_pretraining_amd.ops import fused_optim
+
+    torch.manual_seed(0)
+    g = torch.randn(5_000_003, device=dev(), dtype=torch.bfloat16)
+    ss = [fused_optim.grad_sumsq(g) for _ in range(4)]
+    assert all(torch.equal(ss[0], s) for s in ss[1:]), [float(s) for s in ss]
+    want = g.double().pow(2).sum()
+    print("sumsq rel err", abs(float(ss[0]) - float(want)) / float(want))
+    assert abs(float(ss[0]) - float(want)) <= 1e-4 * float(want)
+
+    N, V = 5000, 256
+    logits = torch.randn(N, V, device=dev(), dtype=torch.bfloat16)
+    targets = torch.randint(0, V, (N,), device=dev())
+    targets[::7] = -100
+    outs = [ext.ce_fwd(logits, targets, -100) for _ in range(4)]  # loss_sum, ntok, lse
+    assert all(torch.equal(outs[0][0], o[0]) for o in outs[1:]), [float(o[0]) for o in outs]
+    loss_sum, ntok, lse = outs[0]
+    assert ntok.item() == (targets != -100).sum().item()
+    ref_lse = torch.logsumexp(logits.double(), dim=-1)
+    print("lse max abs err", float((lse.double() - ref_lse).abs().max()))
+    assert torch.allclose(lse.double(), ref_lse, rtol=0, atol=1e-5)
+    ref_sum = torch.nn.functional.cross_entropy(
+        logits.double(), targets, ignore_index=-100, reduction="sum")
+    print("ce sum rel err", abs(float(loss_sum) - float(ref_sum)) / float(ref_sum))
+    assert abs(float(loss_sum) - float(ref_sum)) <= 1e-5 * float(ref_sum)
+
+
 def test_lion_sgd_gpu(ext):
     from mlx_cuda_distributed_pretraining_amd.ops import fused_optim
 
