@@ -99,7 +99,18 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
     const float* __restrict__ lse, const float* __restrict__ drow,
     __hip_bfloat16* __restrict__ dq, const float* __restrict__ slopes,
     int B, int Sq, int Skv, int Hq, int Hkv, float scale, int modarg,
-    long q_rs, long k_rs, long v_rs, long do_rs, long dq_rs) {
+    long q_rs, long k_rs, long v_rs, long do_rs, long dq_rs,
+    // MOD_BLOCKMASK only: the forward's device mask tensors (attn_fwd.hip)
+    //   mb_gran  uint8 [B,H,ceil(Sq/32),ceil(Skv/64)] 0=masked 1=bits 2=full
+    //   mb_bits  uint8 [B,H,Sq,ceil(Skv/8)] per-element keep bits
+    //   mb_range int32 [B,H,ceil(Sq/256),2] first/last+1 live 64-row kv tile
+    //   bias     bf16  [B,H,Sq,Skv] optional additive score bias (score_mod)
+    const unsigned char* __restrict__ mb_gran = nullptr,
+    const unsigned char* __restrict__ mb_bits = nullptr,
+    const int* __restrict__ mb_range = nullptr,
+    const __hip_bfloat16* __restrict__ bias = nullptr) {
+  // the mask tensors are laid out for the forward's 256-row q blocks
+  static_assert(MOD != MOD_BLOCKMASK || NW == 8, "blockmask bwd is NW=8 only");
   constexpr int TPB = NW * WAVE;
   constexpr int QPB = 32 * NW;
   constexpr int DBLK = D / 16;
@@ -157,6 +168,29 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
     kv_lo = max(0, blk_qpos_lo - modarg + 1) & ~(KVB - 1);
   } else if constexpr (MOD == MOD_PREFIX_LM) {
     kv_hi = min(Skv, max(blk_qpos_hi + 1, modarg));
+  } else if constexpr (MOD == MOD_BLOCKMASK) {
+    // live 64-row kv tiles of this 256-row q block; kv_lo rounds down to this
+    // kernel's own tile (128 rows at D=64) — the extra granule is code 0
+    const int nqpb = (Sq + QPB - 1) / QPB;
+    const int* r = mb_range + (((long)b * Hq + hq) * nqpb + qtile) * 2;
+    kv_lo = (r[0] * 64) & ~(KVB - 1);
+    kv_hi = min(Skv, r[1] * 64);
+    if (kv_hi <= kv_lo) kv_hi = kv_lo;  // fully-masked row block: loop skips
+  }
+  // blockmask: this wave's 32-row granule row and the (b, head) planes of
+  // bits / bias — all block- or wave-uniform, so they live in SGPRs. The
+  // per-lane row offsets are formed inside the masked path (below): D=128
+  // has no VGPRs to spare for row pointers that live across the MFMA loop.
+  const unsigned char* gran_row = nullptr;
+  const unsigned char* bits_bh = nullptr;
+  const __hip_bfloat16* bias_bh = nullptr;
+  [[maybe_unused]] const int kvb8 = (Skv + 7) / 8;
+  if constexpr (MOD == MOD_BLOCKMASK) {
+    const int nq32 = (Sq + 31) / 32;
+    const long bh = (long)b * Hq + hq;
+    gran_row = mb_gran + (bh * nq32 + min(q0w / 32, nq32 - 1)) * (long)((Skv + 63) / 64);
+    bits_bh = mb_bits + bh * Sq * (long)kvb8;
+    if (bias != nullptr) bias_bh = bias + bh * Sq * (long)Skv;
   }
 
   // T14 staging: chunks of (2 kv rows x 8 d); K and V both write row-major.
@@ -218,6 +252,14 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
     for (int hf = 0; hf < KVB / 32; ++hf) {
       const int kvh = kv0 + hf * 32;
       if (kvh >= kv_hi) break;  // block-uniform (kv_hi is block-level)
+      // blockmask: this wave's code for the 64-column granule holding the
+      // sub-tile. Code 0 skips the wave's compute only — no barrier lives
+      // inside this loop, so the block stays in step.
+      [[maybe_unused]] int gcode = 2;
+      if constexpr (MOD == MOD_BLOCKMASK) {
+        gcode = (q0w < Sq) ? __builtin_amdgcn_readfirstlane((int)gran_row[kvh >> 6]) : 0;
+        if (gcode == 0) continue;
+      }
       const __hip_bfloat16* k_lds = smem + buf * TILE + hf * 32 * D;
       const __hip_bfloat16* v_lds = k_lds + KVB * D;
 
@@ -247,6 +289,10 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
         full = full && ((kvh + 31 <= q0w + q_off) || (kvh + 32 <= modarg));
       } else if constexpr (MOD == MOD_ALIBI) {
         full = false;
+      } else if constexpr (MOD == MOD_BLOCKMASK) {
+        // code 2 counts out-of-range elements as live, hence the Sq bound;
+        // a bias is per element, so it rules the mask-free path out
+        full = full && gcode == 2 && bias == nullptr && (q0w + 31 < Sq);
       }
 
       float ds[16];
@@ -254,6 +300,29 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
           const float p = __builtin_amdgcn_exp2f(st[reg] * scale2 - Lq2);
+          ds[reg] = p * (dpt[reg] - Dq) * scale;
+        }
+      } else if constexpr (MOD == MOD_BLOCKMASK) {
+        // this lane's 32 keep bits for the sub-tile, read once into a
+        // register (bit i = k row kvh+i; rows past Skv read as masked)
+        int qr = q_valid ? qrow : 0;
+        // opaque copy: keeps the row-offset multiplies here instead of
+        // hoisted out of the kv loop into long-lived registers
+        asm volatile("" : "+v"(qr));
+        const unsigned char* bits_row = bits_bh + (long)qr * kvb8 + (kvh >> 3);
+        unsigned kbits = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (kvh + 8 * j < Skv) kbits |= (unsigned)bits_row[j] << (8 * j);
+        const __hip_bfloat16* bias_row =
+            (bias != nullptr) ? bias_bh + (long)qr * Skv + kvh : nullptr;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const int kr = acc_row(reg, hi);
+          const bool keep = q_valid && kvh + kr < Skv && ((kbits >> kr) & 1);
+          float s2 = st[reg] * scale2;
+          if (bias_row != nullptr && keep) s2 += __bfloat162float(bias_row[kr]) * LOG2E;
+          const float p = keep ? __builtin_amdgcn_exp2f(s2 - Lq2) : 0.f;
           ds[reg] = p * (dpt[reg] - Dq) * scale;
         }
       } else {
@@ -297,10 +366,17 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
   }
 
   // store dq: element (r=q_local, c=d_local)
-  const int dl = lane & 31;
+  int dl = lane & 31, hi_st = hi;
+  if constexpr (MOD == MOD_BLOCKMASK) {
+    // lane id re-derived here: at D=128 the kernel sits on the 256-VGPR
+    // limit and a lane index kept live across the kv loop spilled
+    const int l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    dl = l & 31;
+    hi_st = l >> 5;
+  }
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
-    const int r = acc_row(reg, hi);
+    const int r = acc_row(reg, hi_st);
     const int q_r = q0w + r;
     if (q_r >= Sq) continue;
     __hip_bfloat16* dqr = dq + ((long)b * Sq + q_r) * dq_rs + (long)hq * D + dl;
@@ -318,7 +394,15 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
     const float* __restrict__ lse, const float* __restrict__ drow,
     __hip_bfloat16* __restrict__ dkv_out, const float* __restrict__ slopes,
     int B, int Sq, int Skv, int Hq, int Hkv, float scale, int modarg,
-    long q_rs, long k_rs, long v_rs, long do_rs, long dkv_rs) {
+    long q_rs, long k_rs, long v_rs, long do_rs, long dkv_rs,
+    // MOD_BLOCKMASK only: mb_gran / mb_bits / bias as in the dQ kernel
+    // (indexed by the q head), plus the transpose of the forward's range:
+    //   mb_qrange int32 [B,H,ceil(Skv/256),2] first/last+1 live 32-row q tile
+    const unsigned char* __restrict__ mb_gran = nullptr,
+    const unsigned char* __restrict__ mb_bits = nullptr,
+    const int* __restrict__ mb_qrange = nullptr,
+    const __hip_bfloat16* __restrict__ bias = nullptr) {
+  static_assert(MOD != MOD_BLOCKMASK || NW == 8, "blockmask bwd is NW=8 only");
   constexpr int TPB = NW * WAVE;
   constexpr int KPB = 32 * NW;
   constexpr int DBLK = D / 16;
@@ -371,7 +455,29 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
     for (int r = 0; r < 16; ++r) acc_out[dc][r] = 0.f;
 
   int q_lo, q_hi;
-  q_range_for_kv<MOD>(kvtile * KPB, KPB, q_off, Sq, modarg, q_lo, q_hi);
+  if constexpr (MOD == MOD_BLOCKMASK) {
+    // union of the live q-tile ranges over this kv head's GQA group, so the
+    // flat (head, q tile) iteration below stays uniform; heads with nothing
+    // live in part of it skip per wave on granule code 0
+    const int nkpb = (Skv + KPB - 1) / KPB;
+    int t_lo = 0x7fffffff, t_hi = 0;
+    for (int g = 0; g < group; ++g) {
+      const int* r = mb_qrange + (((long)b * Hq + hkv * group + g) * nkpb + kvtile) * 2;
+      if (r[1] > r[0]) {
+        t_lo = min(t_lo, r[0]);
+        t_hi = max(t_hi, r[1]);
+      }
+    }
+    q_lo = (t_hi > 0) ? t_lo * 32 : 0;
+    q_hi = (t_hi > 0) ? min(Sq, t_hi * 32) : 0;  // empty: straight to store
+  } else {
+    q_range_for_kv<MOD>(kvtile * KPB, KPB, q_off, Sq, modarg, q_lo, q_hi);
+  }
+  // blockmask per-wave constants: granule column of this wave's 32 k rows
+  // (inside one 64-column granule), this lane's byte/bit in a bits row
+  [[maybe_unused]] const int nq32 = (Sq + 31) / 32;
+  [[maybe_unused]] const int nkvt = (Skv + 63) / 64;
+  [[maybe_unused]] const int kvb8 = (Skv + 7) / 8;
 
   // sub-tiles per barrier: dV runs two (32 MFMAs/barrier, 220-238 VGPR);
   // dK holds V fragments too and spills at NP=2, so it stays at one.
@@ -481,90 +587,123 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
         const __hip_bfloat16* q_lds = smem + buf * TILE + s * 32 * D;
         const __hip_bfloat16* do_lds = smem + buf * TILE + 64 * D + s * 32 * D;
 
-        // S = mfma(Q, K^T): A=Q rm frags from LDS, B = register kf.
-        // element (r=q_local, c=k_local)
-        f32x16 s_acc = {}, dp_acc = {};
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int dblk = 0; dblk < DBLK; ++dblk) {
-          const int off = rm_swz<D>(lk, dblk * 16 + hi * 8);
-          Bf16x8U qa;
-          *reinterpret_cast<uint4*>(qa.s) = *reinterpret_cast<const uint4*>(q_lds + off);
-          s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa.v, kf[dblk], s_acc, 0, 0, 0);
-          if constexpr (WANT_DK) {
-            Bf16x8U da;
-            *reinterpret_cast<uint4*>(da.s) = *reinterpret_cast<const uint4*>(do_lds + off);
-            dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da.v, vf[dblk], dp_acc, 0, 0, 0);
-          }
+        // blockmask: the wave's 32 k rows lie inside one 64-column granule;
+        // the code is per q head. Code 0 skips the wave's compute only — the
+        // staging epilogue and the barrier below still run.
+        [[maybe_unused]] int gcode = 2;
+        if constexpr (MOD == MOD_BLOCKMASK) {
+          const long gi = (((long)b * Hq + hq_) * nq32 + (q0 >> 5)) * (long)nkvt + (kv0w >> 6);
+          gcode = (kv0w < Skv) ? __builtin_amdgcn_readfirstlane((int)mb_gran[gi]) : 0;
         }
-        __builtin_amdgcn_s_setprio(0);
-
-        // interior (q tile entirely below this wave's k rows): mask-free
-        bool full = q0 + 31 < Sq;
-        if constexpr (MOD == MOD_CAUSAL) {
-          full = full && (q0 + q_off >= kv0w + 31);
-        } else if constexpr (MOD == MOD_SLIDING_WINDOW) {
-          full = full && (q0 + q_off >= kv0w + 31) &&
-                 ((q0 + 31 + q_off) - kv0w < modarg);
-        } else if constexpr (MOD == MOD_PREFIX_LM) {
-          // second clause wave-uniform: whole wave's k rows inside the prefix
-          full = full && ((q0 + q_off >= kv0w + 31) || (kv0w + 31 < modarg));
-        } else {
-          full = false;  // MOD_NONE boundary Sq checks + ALIBI slope
-        }
-
-        float pv[16];
-        if (full) {
+        if (MOD != MOD_BLOCKMASK || gcode != 0) {
+          // S = mfma(Q, K^T): A=Q rm frags from LDS, B = register kf.
+          // element (r=q_local, c=k_local)
+          f32x16 s_acc = {}, dp_acc = {};
+          __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-          for (int reg = 0; reg < 16; ++reg) {
-            const int qr = s * 32 + acc_row(reg, hi);
-            const float p = __builtin_amdgcn_exp2f(s_acc[reg] * scale2 - stats_lds[buf][0][qr]);
+          for (int dblk = 0; dblk < DBLK; ++dblk) {
+            const int off = rm_swz<D>(lk, dblk * 16 + hi * 8);
+            Bf16x8U qa;
+            *reinterpret_cast<uint4*>(qa.s) = *reinterpret_cast<const uint4*>(q_lds + off);
+            s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa.v, kf[dblk], s_acc, 0, 0, 0);
             if constexpr (WANT_DK) {
-              pv[reg] = p * (dp_acc[reg] - stats_lds[buf][1][qr]) * scale;  // dS
-            } else {
-              pv[reg] = p;
+              Bf16x8U da;
+              *reinterpret_cast<uint4*>(da.s) = *reinterpret_cast<const uint4*>(do_lds + off);
+              dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da.v, vf[dblk], dp_acc, 0, 0, 0);
             }
           }
-        } else {
+          __builtin_amdgcn_s_setprio(0);
+
+          // interior (q tile entirely below this wave's k rows): mask-free
+          bool full = q0 + 31 < Sq;
+          if constexpr (MOD == MOD_CAUSAL) {
+            full = full && (q0 + q_off >= kv0w + 31);
+          } else if constexpr (MOD == MOD_SLIDING_WINDOW) {
+            full = full && (q0 + q_off >= kv0w + 31) &&
+                   ((q0 + 31 + q_off) - kv0w < modarg);
+          } else if constexpr (MOD == MOD_PREFIX_LM) {
+            // second clause wave-uniform: whole wave's k rows inside the prefix
+            full = full && ((q0 + q_off >= kv0w + 31) || (kv0w + 31 < modarg));
+          } else if constexpr (MOD == MOD_BLOCKMASK) {
+            // code 2 counts out-of-range elements as live, hence the bounds;
+            // a bias is per element, so it rules the mask-free path out
+            full = full && gcode == 2 && bias == nullptr && (kv0w + 31 < Skv);
+          } else {
+            full = false;  // MOD_NONE boundary Sq checks + ALIBI slope
+          }
+
+          float pv[16];
+          if (full) {
 #pragma unroll
-          for (int reg = 0; reg < 16; ++reg) {
-            const int qr = acc_row(reg, hi);
-            const int q_r = q0 + qr;
-            const int q_pos = q_r + q_off;
-            const int k_pos = krow;
-            const bool keep = k_valid && q_r < Sq && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
-            float s2 = s_acc[reg] * scale2;
-            if constexpr (MOD == MOD_ALIBI) s2 += slope2 * (k_pos - q_pos);
-            const float p =
-                keep ? __builtin_amdgcn_exp2f(s2 - stats_lds[buf][0][s * 32 + qr]) : 0.f;
-            if constexpr (WANT_DK) {
-              pv[reg] = p * (dp_acc[reg] - stats_lds[buf][1][s * 32 + qr]) * scale;  // dS
-            } else {
-              pv[reg] = p;
+            for (int reg = 0; reg < 16; ++reg) {
+              const int qr = s * 32 + acc_row(reg, hi);
+              const float p = __builtin_amdgcn_exp2f(s_acc[reg] * scale2 - stats_lds[buf][0][qr]);
+              if constexpr (WANT_DK) {
+                pv[reg] = p * (dp_acc[reg] - stats_lds[buf][1][qr]) * scale;  // dS
+              } else {
+                pv[reg] = p;
+              }
+            }
+          } else {
+            // blockmask: the lane holds ONE k column and 16 q rows, so its
+            // keep bits sit in 16 different bits rows (partial granules only)
+            [[maybe_unused]] const unsigned char* bits_h = nullptr;
+            [[maybe_unused]] const __hip_bfloat16* bias_h = nullptr;
+            if constexpr (MOD == MOD_BLOCKMASK) {
+              const long bh = (long)b * Hq + hq_;
+              bits_h = mb_bits + bh * Sq * (long)kvb8 + (krow >> 3);
+              if (bias != nullptr) bias_h = bias + bh * Sq * (long)Skv + krow;
+            }
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+              const int qr = acc_row(reg, hi);
+              const int q_r = q0 + qr;
+              const int q_pos = q_r + q_off;
+              const int k_pos = krow;
+              bool keep;
+              if constexpr (MOD == MOD_BLOCKMASK) {
+                keep = k_valid && q_r < Sq;
+                if (keep) keep = (bits_h[(long)q_r * kvb8] >> (krow & 7)) & 1;
+              } else {
+                keep = k_valid && q_r < Sq && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
+              }
+              float s2 = s_acc[reg] * scale2;
+              if constexpr (MOD == MOD_ALIBI) s2 += slope2 * (k_pos - q_pos);
+              if constexpr (MOD == MOD_BLOCKMASK) {
+                if (bias != nullptr && keep)
+                  s2 += __bfloat162float(bias_h[(long)q_r * Skv]) * LOG2E;
+              }
+              const float p =
+                  keep ? __builtin_amdgcn_exp2f(s2 - stats_lds[buf][0][s * 32 + qr]) : 0.f;
+              if constexpr (WANT_DK) {
+                pv[reg] = p * (dp_acc[reg] - stats_lds[buf][1][s * 32 + qr]) * scale;  // dS
+              } else {
+                pv[reg] = p;
+              }
             }
           }
-        }
 
-        // transform: acc holds M[r=q][c=k]; A-frags of M^T = dS^T (dK) / P^T (dV)
-        bf16x8 a0, a1;
-        acc_to_afrag(pv, a0, a1);
-        __builtin_amdgcn_s_setprio(1);
+          // transform: acc holds M[r=q][c=k]; A-frags of M^T = dS^T (dK) / P^T (dV)
+          bf16x8 a0, a1;
+          acc_to_afrag(pv, a0, a1);
+          __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int dc = 0; dc < DCOL; ++dc) {
-          f32x16 acc;
+          for (int dc = 0; dc < DCOL; ++dc) {
+            f32x16 acc;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = acc_out[dc][r];
+            for (int r = 0; r < 16; ++r) acc[r] = acc_out[dc][r];
 #pragma unroll
-          for (int ks = 0; ks < 2; ++ks) {
-            // B = X[16q x 32d] (X = Q for dK, dO for dV): tr_read from rm image
-            bf16x8 xb = tr16_frag<D>(WANT_DK ? q_lds : do_lds, ks * 16 + hi * 8,
-                                     dc * 32, lane);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks == 0 ? a0 : a1, xb, acc, 0, 0, 0);
+            for (int ks = 0; ks < 2; ++ks) {
+              // B = X[16q x 32d] (X = Q for dK, dO for dV): tr_read from rm image
+              bf16x8 xb = tr16_frag<D>(WANT_DK ? q_lds : do_lds, ks * 16 + hi * 8,
+                                       dc * 32, lane);
+              acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks == 0 ? a0 : a1, xb, acc, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc_out[dc][r] = acc[r];
           }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc_out[dc][r] = acc[r];
+          __builtin_amdgcn_s_setprio(0);
         }
-        __builtin_amdgcn_s_setprio(0);
 
         // split-half staging epilogue: write the half that loaded during
         // this half's compute, then start the next half's load
@@ -744,6 +883,103 @@ std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, a
                         lse.data_ptr<float>(), drow.data_ptr<float>(), dqp, dkp, dvp, sl,
                         B, Sq, Skv, Hq, Hkv, (float)scale, (int)modarg, q_rs, k_rs, v_rs, do_rs,
                         dq_rs, dk_rs, dv_rs);
+  return {dq, dk, dv};
+}
+
+// Backward of attn_fwd_blockmask (trainable flex attention): same device mask
+// tensors as the forward plus qrange, the per-kv-block transpose of range.
+// Always 8 waves/block: the mask tensors are laid out for 256-row blocks, so
+// MCDP_ATTN_BWD_NW does not apply here. bias (may be empty) gets no gradient.
+std::vector<at::Tensor> attn_bwd_blockmask(at::Tensor q, at::Tensor k, at::Tensor v,
+                                           at::Tensor o, at::Tensor dout, at::Tensor lse,
+                                           double scale, at::Tensor gran, at::Tensor bits,
+                                           at::Tensor range, at::Tensor qrange,
+                                           at::Tensor bias) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "attn_bwd_blockmask: bf16 only");
+  auto rs = [](at::Tensor& t) {
+    const int S = t.size(1), D = t.size(3);
+    if (!(t.stride(3) == 1 && t.stride(2) == D && t.stride(0) == (long)S * t.stride(1)))
+      t = t.contiguous();
+    return t.stride(1);
+  };
+  const long q_rs = rs(q), k_rs = rs(k), v_rs = rs(v), do_rs = rs(dout);
+  o = o.contiguous();
+  lse = lse.contiguous();
+  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
+  const int Skv = k.size(1), Hkv = k.size(2);
+  TORCH_CHECK(Hq % Hkv == 0 && (D == 64 || D == 128),
+              "attn_bwd_blockmask: GQA needs Hq % Hkv == 0, head_dim 64 or 128");
+  TORCH_CHECK(k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16 &&
+              k.size(0) == B && k.size(3) == D && v.sizes() == k.sizes() &&
+              o.sizes() == q.sizes() && dout.sizes() == q.sizes(),
+              "attn_bwd_blockmask: q/k/v/o/dout shape mismatch");
+  TORCH_CHECK(dout.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16 &&
+              lse.scalar_type() == at::kFloat && lse.numel() == (long)B * Hq * Sq,
+              "attn_bwd_blockmask: o/dout bf16, lse f32 [B,H,S]");
+  TORCH_CHECK(gran.scalar_type() == at::kByte && bits.scalar_type() == at::kByte &&
+              range.scalar_type() == at::kInt && qrange.scalar_type() == at::kInt,
+              "blockmask tensor dtypes");
+  TORCH_CHECK(gran.is_cuda() && bits.is_cuda() && range.is_cuda() && qrange.is_cuda(),
+              "blockmask tensors must be on the GPU");
+  gran = gran.contiguous();
+  bits = bits.contiguous();
+  range = range.contiguous();
+  qrange = qrange.contiguous();
+  constexpr int BLK = 8 * 32;  // q rows (dQ) / kv rows (dK, dV) per block
+  auto shape_is = [](const at::Tensor& t, long a, long b_, long c, long d) {
+    return t.dim() == 4 && t.size(0) == a && t.size(1) == b_ && t.size(2) == c && t.size(3) == d;
+  };
+  TORCH_CHECK(shape_is(gran, B, Hq, cdiv(Sq, 32), cdiv(Skv, 64)), "gran shape mismatch");
+  TORCH_CHECK(shape_is(bits, B, Hq, Sq, cdiv(Skv, 8)), "bits shape mismatch");
+  TORCH_CHECK(shape_is(range, B, Hq, cdiv(Sq, BLK), 2), "range shape mismatch");
+  TORCH_CHECK(shape_is(qrange, B, Hq, cdiv(Skv, BLK), 2), "qrange shape mismatch");
+  const bool has_bias = bias.numel() > 0;
+  if (has_bias) {
+    TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kBFloat16 &&
+                shape_is(bias, B, Hq, Sq, Skv), "bias must be bf16 [B,H,Sq,Skv]");
+    bias = bias.contiguous();
+  }
+  auto dq = at::empty({B, Sq, Hq, D}, q.options());
+  auto dk = at::empty({B, Skv, Hkv, D}, q.options());
+  auto dv = at::empty({B, Skv, Hkv, D}, q.options());
+  auto drow = at::empty({(long)B * Sq * Hq}, q.options().dtype(at::kFloat));
+  auto stream = at::cuda::getCurrentHIPStream();
+  {  // preprocess, as in attn_bwd_out
+    const long rows = (long)B * Sq * Hq;
+    const int rpw = WAVE / (D / 8);
+    const long grid = cdiv(rows, (long)(256 / WAVE) * rpw);
+    bwd_preprocess_kernel<<<grid, 256, 0, stream>>>(
+        reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
+        reinterpret_cast<const __hip_bfloat16*>(o.data_ptr()),
+        drow.data_ptr<float>(), rows, D, do_rs, Hq);
+  }
+  dim3 gq(cdiv(Sq, BLK), Hq, B), gkv(cdiv(Skv, BLK), Hkv, B), block(8 * WAVE);
+  auto* qp = reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
+  auto* kp = reinterpret_cast<const __hip_bfloat16*>(k.data_ptr());
+  auto* vp = reinterpret_cast<const __hip_bfloat16*>(v.data_ptr());
+  auto* dop = reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr());
+  auto* bp = has_bias ? reinterpret_cast<const __hip_bfloat16*>(bias.data_ptr()) : nullptr;
+  const float* lp = lse.data_ptr<float>();
+  const float* drp = drow.data_ptr<float>();
+  const unsigned char* gp = gran.data_ptr<unsigned char>();
+  const unsigned char* bitp = bits.data_ptr<unsigned char>();
+  auto launch = [&](auto dtag) {
+    constexpr int DD = decltype(dtag)::value;
+    attn_bwd_dq_kernel<DD, MOD_BLOCKMASK, 8><<<gq, block, 0, stream>>>(
+        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()), nullptr,
+        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dq.stride(1),
+        gp, bitp, range.data_ptr<int>(), bp);
+    attn_bwd_dkv_kernel<DD, MOD_BLOCKMASK, true, 8><<<gkv, block, 0, stream>>>(
+        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()), nullptr,
+        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dk.stride(1),
+        gp, bitp, qrange.data_ptr<int>(), bp);
+    attn_bwd_dkv_kernel<DD, MOD_BLOCKMASK, false, 8><<<gkv, block, 0, stream>>>(
+        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()), nullptr,
+        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dv.stride(1),
+        gp, bitp, qrange.data_ptr<int>(), bp);
+  };
+  if (D == 64) launch(std::integral_constant<int, 64>{});
+  else launch(std::integral_constant<int, 128>{});
   return {dq, dk, dv};
 }
 

@@ -52,6 +52,11 @@ std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, a
                                      at::Tensor dout, at::Tensor lse, double scale, long mod,
                                      long modarg, at::Tensor slopes,
                                      at::Tensor dq, at::Tensor dk, at::Tensor dv);
+std::vector<at::Tensor> attn_bwd_blockmask(at::Tensor q, at::Tensor k, at::Tensor v,
+                                           at::Tensor o, at::Tensor dout, at::Tensor lse,
+                                           double scale, at::Tensor gran, at::Tensor bits,
+                                           at::Tensor range, at::Tensor qrange,
+                                           at::Tensor bias);
 // sampling.hip
 at::Tensor sample_token(at::Tensor logits, double temperature, double top_p, double min_p,
                         long seed);
@@ -110,6 +115,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd, "flash attention backward (dq, dk, dv)");
   m.def("attn_bwd_out", &attn_bwd_out,
         "flash attention backward into strided out views (fused dQKV)");
+  m.def("attn_bwd_blockmask", &attn_bwd_blockmask,
+        "backward of attn_fwd_blockmask (dq, dk, dv); bias gets no gradient");
   m.def("sample_token", &sample_token, "fused temperature/min-p sampling");
   m.def("sample_token_dev", &sample_token_dev,
         "graph-capturable sampling (device position salt)");

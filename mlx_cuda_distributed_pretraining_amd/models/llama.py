@@ -25,7 +25,10 @@ from typing import Any, Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from ..ops.attention import attention_ref, flash_attention, rope_flash_attention_qkv
+from ..ops.attention import (
+    CompiledBlockMask, attention_ref, flash_attention, flex_attention,
+    rope_flash_attention_qkv,
+)
 from ..ops.gemv import FastLinear, linear_fast
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
 from ..parallel.tp import copy_to_tp, gather_sp, reduce_from_tp, scatter_sp, tp_group
@@ -148,6 +151,7 @@ class Attention(nn.Module):
         self.wo = FastLinear(self.n_heads * self.head_dim, args.hidden_size, bias=args.attention_bias)
         self.wqkv.fp8 = self.wo.fp8 = args.fp8
         self.rope_table = rope_table
+        self.flex_mask = None  # set through Model.set_flex_mask
         if args.use_alibi:
             slopes = torch.tensor(
                 [2 ** (-8.0 * (i + 1) / self.n_heads) for i in range(self.n_heads)]
@@ -173,6 +177,32 @@ class Attention(nn.Module):
             return self.wo(o.reshape(B, S, -1))  # static decode is TP-free
 
         atype = self.args.attention_type
+        if self.flex_mask is not None and cache is None:
+            # custom mask (Model.set_flex_mask): unfused qkv split + RoPE,
+            # then flex_attention — on bf16 GPU inputs that is the
+            # MOD_BLOCKMASK kernels forward and backward
+            q, k, v = qkv.split(
+                [
+                    self.n_heads * self.head_dim,
+                    self.n_kv_heads * self.head_dim,
+                    self.n_kv_heads * self.head_dim,
+                ],
+                dim=-1,
+            )
+            cos, sin = self.rope_table.get(S, x.device, 0)
+            q = apply_rope(q.view(B, S, self.n_heads, self.head_dim), cos, sin,
+                           self.args.rope_traditional, 0)
+            k = apply_rope(k.view(B, S, self.n_kv_heads, self.head_dim), cos, sin,
+                           self.args.rope_traditional, 0)
+            v = v.view(B, S, self.n_kv_heads, self.head_dim)
+            if isinstance(self.flex_mask, CompiledBlockMask):
+                o = flex_attention(q, k, v, block_mask=self.flex_mask, scale=self.scale)
+            else:
+                o = flex_attention(q, k, v, mask_mod=self.flex_mask, scale=self.scale)
+            out = self.wo(o.reshape(B, S, -1))
+            if getattr(self, "_sp", False) and self.training:
+                return scatter_sp(out)
+            return reduce_from_tp(out) if getattr(self, "_tp", False) else out
         if cache is None and atype != "simple":
             # training fast path: one fused autograd node over the fused QKV
             # tensor (RoPE + attention; backward writes dQKV in place — no
@@ -492,6 +522,22 @@ class Model(nn.Module):
                 nn.init.zeros_(module.bias)
         elif isinstance(module, nn.Embedding):
             nn.init.normal_(module.weight, mean=0.0, std=0.02)
+
+    def set_flex_mask(self, mask) -> None:
+        """Train / evaluate with a custom attention mask on every layer.
+
+        ``mask`` is a ``mask_mod(b, h, q_idx, kv_idx) -> bool`` callable, a
+        ``CompiledBlockMask`` (compile once, reuse across steps — a callable
+        is recompiled on every forward), or ``None`` to return to the
+        configured attention. The mask REPLACES the built-in causal mask, so
+        a causal model wants ``ki <= qi`` inside it, and every query row
+        needs at least one live key (see ``flex_attention``). It applies to
+        full-sequence forwards only: the KV-cache and static-decode paths
+        ignore it. The attention_type "simple" parity path is bypassed while
+        a mask is set.
+        """
+        for layer in self.layers:
+            layer.attention.flex_mask = mask
 
     def forward(
         self, tokens: torch.Tensor, cache: Optional[List[KVCache]] = None

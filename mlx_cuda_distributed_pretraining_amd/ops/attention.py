@@ -302,9 +302,24 @@ def flex_attention(
     /root/reference/models/attention/flex_attention.py:414-562).
 
     Named patterns route to the kernel (causal / sliding_window / prefix_lm /
-    alibi via ``block_mask.pattern``); arbitrary Python callables run on the
-    fp32 reference path (GPU included — they are inherently per-element
-    Python and exist for parity/experimentation, not the hot path).
+    alibi via ``block_mask.pattern``). An arbitrary ``mask_mod`` on bf16 GPU
+    inputs (or a ``CompiledBlockMask``) is compiled to device mask tensors
+    and runs the MFMA kernels forward AND backward (MOD_BLOCKMASK in
+    csrc/attn_fwd.hip / csrc/attn_bwd.hip), so it trains; an additive
+    ``score_mod`` rides along as a precomputed bias. Everything else — CPU,
+    other dtypes, a non-additive ``score_mod``, or a ``score_mod`` whose bias
+    itself requires grad — runs the fp32 reference composition, which keeps
+    correct gradients but materializes S x S scores.
+
+    Limits of the trainable kernel path:
+      * Every query row needs at least one live key. A fully masked row is
+        0 * (1/0) in the forward kernel's epilogue and poisons that row's
+        gradients; the reference composition zeroes such rows instead.
+      * ``score_mod`` is evaluated ONCE into a bf16 [B, H, S, KV] bias that
+        is kept for the backward: O(S^2) memory, and the bias (e.g. a
+        learned table) gets no gradient on this path.
+      * The mask tensors are laid out for 256-row blocks, so the backward
+        always runs 8 waves per block; MCDP_ATTN_BWD_NW does not apply.
     """
     if isinstance(block_mask, CompiledBlockMask):
         return _flex_blockmask(q, k, v, block_mask, score_mod, scale)
@@ -320,23 +335,54 @@ def flex_attention(
         )
     if score_mod is None and mask_mod is None:
         return flash_attention(q, k, v, causal=True, scale=scale)
-    if (mask_mod is not None and q.is_cuda and not torch.is_grad_enabled()
-            and q.dtype == torch.bfloat16):
+    if mask_mod is not None and q.is_cuda and q.dtype == torch.bfloat16:
         bm = CompiledBlockMask(mask_mod, q.shape[0], q.shape[2], q.shape[1],
                                k.shape[1], device=q.device)
         return _flex_blockmask(q, k, v, bm, score_mod, scale)
     return attention_ref(q, k, v, causal=False, scale=scale, score_mod=score_mod, mask_mod=mask_mod)
 
 
+class _FlexBlockMaskFn(torch.autograd.Function):
+    """attn_fwd_blockmask / attn_bwd_blockmask as one autograd node. ``bias``
+    is the score_mod bias evaluated once by the caller (empty = none); it is
+    saved for the backward, never recomputed, and gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, bm, scale):
+        from ._ext import require_ext
+
+        o, lse = require_ext().attn_fwd_blockmask(q, k, v, scale, bm.gran, bm.bits,
+                                                  bm.range, bias)
+        ctx.save_for_backward(q, k, v, o, lse, bias)
+        ctx.bm, ctx.scale = bm, scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        from ._ext import require_ext
+
+        q, k, v, o, lse, bias = ctx.saved_tensors
+        bm = ctx.bm
+        dq, dk, dv = require_ext().attn_bwd_blockmask(
+            q, k, v, o, do, lse, ctx.scale, bm.gran, bm.bits, bm.range, bm.qrange, bias)
+        return dq, dk, dv, None, None, None
+
+
 def _flex_blockmask(q, k, v, bm: "CompiledBlockMask", score_mod, scale):
     """Kernel-path flex: compiled mask tensors + (optional) a precomputed
     additive bias tensor for score_mod (evaluated vectorized once; the
-    kernel adds it pre-softmax). Inference/eval surface — with grads the
-    caller stays on the autograd fp32 path."""
+    kernel adds it pre-softmax). With grads it runs as _FlexBlockMaskFn
+    (HIP forward + backward); what the kernels cannot differentiate falls
+    back to the fp32 composition."""
     from ._ext import require_ext
 
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
+    if needs_grad and not use_hip(q, k, v, dtypes=(torch.bfloat16,)):
+        # CPU / non-bf16 training: the composition differentiates itself
+        return attention_ref(q, k, v, causal=False, scale=scale, score_mod=score_mod,
+                             mask_mod=bm._mask_mod)
     bias = torch.empty(0, dtype=torch.bfloat16, device=q.device)
     if score_mod is not None:
         B, S, H, D = q.shape
@@ -357,7 +403,16 @@ def _flex_blockmask(q, k, v, bm: "CompiledBlockMask", score_mod, scale):
                                  score_mod=score_mod,
                                  mask_mod=getattr(bm, "_mask_mod", None))
         zero = torch.zeros(B, H, S, KV, device=q.device)
-        bias = score_mod(zero, bi, hi, qi, ki).to(torch.bfloat16)
+        bias = score_mod(zero, bi, hi, qi, ki)
+        if needs_grad and bias.requires_grad:
+            # the bias depends on a trainable tensor (e.g. a learned table):
+            # the kernels give it no gradient, the composition does
+            return attention_ref(q, k, v, causal=False, scale=scale,
+                                 score_mod=score_mod,
+                                 mask_mod=getattr(bm, "_mask_mod", None))
+        bias = bias.detach().to(torch.bfloat16)
+    if needs_grad:
+        return _FlexBlockMaskFn.apply(q, k, v, bias, bm, float(scale))
     o, _ = require_ext().attn_fwd_blockmask(q, k, v, float(scale), bm.gran,
                                             bm.bits, bm.range, bias)
     return o
@@ -401,6 +456,9 @@ class CompiledBlockMask:
       bits  [B,H,Q,ceil(KV/8)]            packed keep bits
       range [B,H,ceil(Q/256),2]           first / last+1 live kv tile per
                                           256-row kernel block
+      qrange [B,H,ceil(KV/256),2]         first / last+1 live 32-row q tile
+                                          per 256-row kv block (backward:
+                                          the dK/dV kernels' q loop bounds)
     """
 
     KVB = 64
@@ -419,6 +477,8 @@ class CompiledBlockMask:
         self.bits = torch.zeros(B, H, Q_LEN, (KV_LEN + 7) // 8, dtype=torch.uint8,
                                 device=device)
         self.range = torch.zeros(B, H, nqpb, 2, dtype=torch.int32, device=device)
+        nkpb = (KV_LEN + self.QPB - 1) // self.QPB  # the backward's kv blocks
+        self.qrange = torch.zeros(B, H, nkpb, 2, dtype=torch.int32, device=device)
         weights = (1 << torch.arange(8, device=device, dtype=torch.int32)).to(torch.uint8)
         for b in range(B):
             for h in range(H):
@@ -452,6 +512,14 @@ class CompiledBlockMask:
                     if live.numel():
                         self.range[b, h, qb, 0] = int(live.min())
                         self.range[b, h, qb, 1] = int(live.max()) + 1
+                # transpose of range for the dK/dV kernels: per 256-row kv
+                # block (4 granule columns), first/last+1 live 32-row q tile
+                for kb in range(nkpb):
+                    cols = any_live[:, kb * 4:(kb + 1) * 4]
+                    live = cols.any(dim=1).nonzero().flatten()
+                    if live.numel():
+                        self.qrange[b, h, kb, 0] = int(live.min())
+                        self.qrange[b, h, kb, 1] = int(live.max()) + 1
 
 
 def create_block_mask(
