@@ -108,9 +108,12 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
     const unsigned char* __restrict__ mb_gran = nullptr,
     const unsigned char* __restrict__ mb_bits = nullptr,
     const int* __restrict__ mb_range = nullptr,
-    const __hip_bfloat16* __restrict__ bias = nullptr) {
+    const __hip_bfloat16* __restrict__ bias = nullptr,
+    // MOD_DOCUMENT only: doc_start int32 [B,Sq] (see attn_fwd.hip)
+    const int* __restrict__ doc_start = nullptr) {
   // the mask tensors are laid out for the forward's 256-row q blocks
   static_assert(MOD != MOD_BLOCKMASK || NW == 8, "blockmask bwd is NW=8 only");
+  static_assert(MOD != MOD_DOCUMENT || NW == 8, "document bwd is built for NW=8 only");
   constexpr int TPB = NW * WAVE;
   constexpr int QPB = 32 * NW;
   constexpr int DBLK = D / 16;
@@ -156,6 +159,17 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
   }
   const float Lq2 = (q_valid ? lse[((long)b * Hq + hq) * Sq + qrow] : INFINITY) * LOG2E;
   const float Dq = q_valid ? drow[((long)b * Sq + qrow) * Hq + hq] : 0.f;
+  // document mask: this lane's lower bound, and the wave's smallest / largest
+  // one (its first / last row's; wave-uniform loads) for the per-wave dead
+  // sub-tile skip and the mask-free test
+  [[maybe_unused]] int dstart = 0, dstart_wmin = 0, dstart_wmax = 0, q0u = q0w;
+  if constexpr (MOD == MOD_DOCUMENT) {
+    const int* ds = doc_start + (long)b * Sq;
+    q0u = __builtin_amdgcn_readfirstlane(q0w);  // the wave's first row, in an SGPR
+    dstart = ds[q_valid ? qrow : 0];
+    dstart_wmin = ds[min(q0u, Sq - 1)];
+    dstart_wmax = ds[min(q0u + 31, Sq - 1)];
+  }
 
   // kv range (same as forward)
   const int blk_qpos_lo = qtile * QPB + q_off;
@@ -176,6 +190,11 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
     kv_lo = (r[0] * 64) & ~(KVB - 1);
     kv_hi = min(Skv, r[1] * 64);
     if (kv_hi <= kv_lo) kv_hi = kv_lo;  // fully-masked row block: loop skips
+  } else if constexpr (MOD == MOD_DOCUMENT) {
+    // the block's first row has the smallest start; kv_lo rounds down to this
+    // kernel's own tile (128 rows at D=64)
+    kv_hi = min(Skv, blk_qpos_hi + 1);
+    kv_lo = doc_clamp(doc_start[(long)b * Sq + qtile * QPB], Skv) & ~(KVB - 1);
   }
   // blockmask: this wave's 32-row granule row and the (b, head) planes of
   // bits / bias — all block- or wave-uniform, so they live in SGPRs. The
@@ -260,6 +279,12 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
         gcode = (q0w < Sq) ? __builtin_amdgcn_readfirstlane((int)gran_row[kvh >> 6]) : 0;
         if (gcode == 0) continue;
       }
+      // document: sub-tiles wholly above the wave's diagonal or wholly in
+      // front of its first row's document are dead for the whole wave — the
+      // same compute-only skip (wave-uniform: all operands are SGPRs)
+      if constexpr (MOD == MOD_DOCUMENT) {
+        if (kvh > q0u + 31 || kvh + 31 < dstart_wmin) continue;
+      }
       const __hip_bfloat16* k_lds = smem + buf * TILE + hf * 32 * D;
       const __hip_bfloat16* v_lds = k_lds + KVB * D;
 
@@ -289,6 +314,9 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
         full = full && ((kvh + 31 <= q0w + q_off) || (kvh + 32 <= modarg));
       } else if constexpr (MOD == MOD_ALIBI) {
         full = false;
+      } else if constexpr (MOD == MOD_DOCUMENT) {
+        // the wave's last row has its largest start
+        full = full && (kvh + 31 <= q0u) && (kvh >= dstart_wmax);
       } else if constexpr (MOD == MOD_BLOCKMASK) {
         // code 2 counts out-of-range elements as live, hence the Sq bound;
         // a bias is per element, so it rules the mask-free path out
@@ -329,7 +357,11 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
           const int k_pos = kvh + acc_row(reg, hi);
-          const bool keep = q_valid && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
+          bool keep;
+          if constexpr (MOD == MOD_DOCUMENT)
+            keep = q_valid && k_pos < Skv && k_pos <= q_pos && k_pos >= dstart;
+          else
+            keep = q_valid && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
           float s2 = st[reg] * scale2;
           if constexpr (MOD == MOD_ALIBI) s2 += slope2 * (k_pos - q_pos);
           const float p = keep ? __builtin_amdgcn_exp2f(s2 - Lq2) : 0.f;
@@ -401,8 +433,12 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
     const unsigned char* __restrict__ mb_gran = nullptr,
     const unsigned char* __restrict__ mb_bits = nullptr,
     const int* __restrict__ mb_qrange = nullptr,
-    const __hip_bfloat16* __restrict__ bias = nullptr) {
+    const __hip_bfloat16* __restrict__ bias = nullptr,
+    // MOD_DOCUMENT only: doc_end int32 [B,Skv], one past the last position of
+    // each row's document (non-decreasing along s; same for every head)
+    const int* __restrict__ doc_end = nullptr) {
   static_assert(MOD != MOD_BLOCKMASK || NW == 8, "blockmask bwd is NW=8 only");
+  static_assert(MOD != MOD_DOCUMENT || NW == 8, "document bwd is built for NW=8 only");
   constexpr int TPB = NW * WAVE;
   constexpr int KPB = 32 * NW;
   constexpr int DBLK = D / 16;
@@ -470,6 +506,12 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
     }
     q_lo = (t_hi > 0) ? t_lo * 32 : 0;
     q_hi = (t_hi > 0) ? min(Sq, t_hi * 32) : 0;  // empty: straight to store
+  } else if constexpr (MOD == MOD_DOCUMENT) {
+    // causal q_lo; the block's last k row has the largest end. An ill-formed
+    // end in front of q_lo leaves an empty range (straight to store).
+    const int kvb0 = kvtile * KPB;
+    q_lo = kvb0 & ~31;
+    q_hi = max(q_lo, doc_clamp(doc_end[(long)b * Skv + min(kvb0 + KPB - 1, Skv - 1)], Sq));
   } else {
     q_range_for_kv<MOD>(kvtile * KPB, KPB, q_off, Sq, modarg, q_lo, q_hi);
   }
@@ -478,6 +520,17 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
   [[maybe_unused]] const int nq32 = (Sq + 31) / 32;
   [[maybe_unused]] const int nkvt = (Skv + 63) / 64;
   [[maybe_unused]] const int kvb8 = (Skv + 7) / 8;
+  // document mask: this lane's upper bound, and the wave's smallest / largest
+  // one (its first / last k row's; wave-uniform loads) for the mask-free test
+  // and the per-wave dead-tile skip
+  [[maybe_unused]] int dend = 0, dend_wmin = 0, dend_wmax = 0, kv0u = kv0w;
+  if constexpr (MOD == MOD_DOCUMENT) {
+    const int* de = doc_end + (long)b * Skv;
+    kv0u = __builtin_amdgcn_readfirstlane(kv0w);  // the wave's first k row, in an SGPR
+    dend = de[k_valid ? krow : 0];
+    dend_wmin = de[min(kv0u, Skv - 1)];
+    dend_wmax = de[min(kv0u + 31, Skv - 1)];
+  }
 
   // sub-tiles per barrier: dV runs two (32 MFMAs/barrier, 220-238 VGPR);
   // dK holds V fragments too and spills at NP=2, so it stays at one.
@@ -595,7 +648,13 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
           const long gi = (((long)b * Hq + hq_) * nq32 + (q0 >> 5)) * (long)nkvt + (kv0w >> 6);
           gcode = (kv0w < Skv) ? __builtin_amdgcn_readfirstlane((int)mb_gran[gi]) : 0;
         }
-        if (MOD != MOD_BLOCKMASK || gcode != 0) {
+        // document: a q tile wholly above the wave's first k row, or wholly
+        // past its last k row's document, is dead for the whole wave — same
+        // compute-only skip (all operands are SGPRs)
+        if constexpr (MOD == MOD_DOCUMENT) {
+          gcode = (kv0u < Skv && q0 + 31 >= kv0u && q0 < dend_wmax) ? 1 : 0;
+        }
+        if ((MOD != MOD_BLOCKMASK && MOD != MOD_DOCUMENT) || gcode != 0) {
           // S = mfma(Q, K^T): A=Q rm frags from LDS, B = register kf.
           // element (r=q_local, c=k_local)
           f32x16 s_acc = {}, dp_acc = {};
@@ -624,6 +683,9 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
           } else if constexpr (MOD == MOD_PREFIX_LM) {
             // second clause wave-uniform: whole wave's k rows inside the prefix
             full = full && ((q0 + q_off >= kv0w + 31) || (kv0w + 31 < modarg));
+          } else if constexpr (MOD == MOD_DOCUMENT) {
+            // the wave's first k row has its smallest end
+            full = full && (q0 >= kv0u + 31) && (q0 + 31 < dend_wmin);
           } else if constexpr (MOD == MOD_BLOCKMASK) {
             // code 2 counts out-of-range elements as live, hence the bounds;
             // a bias is per element, so it rules the mask-free path out
@@ -664,6 +726,8 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
               if constexpr (MOD == MOD_BLOCKMASK) {
                 keep = k_valid && q_r < Sq;
                 if (keep) keep = (bits_h[(long)q_r * kvb8] >> (krow & 7)) & 1;
+              } else if constexpr (MOD == MOD_DOCUMENT) {
+                keep = q_r < Sq && k_valid && q_r >= krow && q_r < dend;
               } else {
                 keep = k_valid && q_r < Sq && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
               }
@@ -981,6 +1045,111 @@ std::vector<at::Tensor> attn_bwd_blockmask(at::Tensor q, at::Tensor k, at::Tenso
   if (D == 64) launch(std::integral_constant<int, 64>{});
   else launch(std::integral_constant<int, 128>{});
   return {dq, dk, dv};
+}
+
+// Backward of attn_fwd_doc (document-masked packed sequences). doc_start /
+// doc_end are int32 [B, S]; dq/dk/dv may be empty (allocated here) or
+// row-strided views into a fused dQKV buffer, as in attn_bwd_out. Built for
+// 8 waves/block only, so MCDP_ATTN_BWD_NW does not apply here.
+std::vector<at::Tensor> attn_bwd_doc_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                         at::Tensor dout, at::Tensor lse, double scale,
+                                         at::Tensor doc_start, at::Tensor doc_end,
+                                         at::Tensor dq, at::Tensor dk, at::Tensor dv) {
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda() && o.is_cuda() && dout.is_cuda() &&
+              lse.is_cuda(), "attn_bwd_doc: GPU tensors only");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 &&
+              v.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16 &&
+              dout.scalar_type() == at::kBFloat16, "attn_bwd_doc: bf16 only");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "attn_bwd_doc: q/k/v must be [B,S,H,D]");
+  auto rs = [](at::Tensor& t) {
+    const int S = t.size(1), D = t.size(3);
+    if (!(t.stride(3) == 1 && t.stride(2) == D && t.stride(0) == (long)S * t.stride(1)))
+      t = t.contiguous();
+    return t.stride(1);
+  };
+  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
+  const int Skv = k.size(1), Hkv = k.size(2);
+  TORCH_CHECK(Sq == Skv, "attn_bwd_doc: document mask is training-only (Sq == Skv), got ",
+              Sq, " vs ", Skv);
+  TORCH_CHECK(Hq % Hkv == 0 && (D == 64 || D == 128),
+              "attn_bwd_doc: GQA needs Hq % Hkv == 0, head_dim 64 or 128");
+  TORCH_CHECK(k.size(0) == B && k.size(3) == D && v.sizes() == k.sizes() &&
+              o.sizes() == q.sizes() && dout.sizes() == q.sizes(),
+              "attn_bwd_doc: q/k/v/o/dout shape mismatch");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (long)B * Hq * Sq,
+              "attn_bwd_doc: lse must be f32 [B,H,S]");
+  auto check_doc = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.scalar_type() == at::kInt && t.is_contiguous() && t.dim() == 2 &&
+                t.size(0) == B && t.size(1) == Sq && t.device() == q.device(),
+                "attn_bwd_doc: ", name, " must be contiguous int32 [B,S] on q's device");
+  };
+  check_doc(doc_start, "doc_start");
+  check_doc(doc_end, "doc_end");
+  const long q_rs = rs(q), k_rs = rs(k), v_rs = rs(v), do_rs = rs(dout);
+  o = o.contiguous();
+  lse = lse.contiguous();
+  auto check_out = [&](at::Tensor& t, int S_, int H_) {
+    if (t.numel() == 0) {
+      t = at::empty({B, S_, H_, D}, q.options());
+    } else {
+      TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.dim() == 4 &&
+                      t.size(0) == B && t.size(1) == S_ && t.size(2) == H_ && t.size(3) == D &&
+                      t.stride(3) == 1 && t.stride(2) == D &&
+                      t.stride(0) == (long)S_ * t.stride(1),
+                  "attn_bwd_doc: bad out view");
+    }
+    return t.stride(1);
+  };
+  const long dq_rs = check_out(dq, Sq, Hq);
+  const long dk_rs = check_out(dk, Skv, Hkv);
+  const long dv_rs = check_out(dv, Skv, Hkv);
+  auto drow = at::empty({(long)B * Sq * Hq}, q.options().dtype(at::kFloat));
+  auto stream = at::cuda::getCurrentHIPStream();
+  {  // preprocess, as in attn_bwd_out
+    const long rows = (long)B * Sq * Hq;
+    const int rpw = WAVE / (D / 8);
+    const long grid = cdiv(rows, (long)(256 / WAVE) * rpw);
+    bwd_preprocess_kernel<<<grid, 256, 0, stream>>>(
+        reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
+        reinterpret_cast<const __hip_bfloat16*>(o.data_ptr()),
+        drow.data_ptr<float>(), rows, D, do_rs, Hq);
+  }
+  constexpr int BLK = 8 * 32;  // q rows (dQ) / kv rows (dK, dV) per block
+  dim3 gq(cdiv(Sq, BLK), Hq, B), gkv(cdiv(Skv, BLK), Hkv, B), block(8 * WAVE);
+  auto* qp = reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
+  auto* kp = reinterpret_cast<const __hip_bfloat16*>(k.data_ptr());
+  auto* vp = reinterpret_cast<const __hip_bfloat16*>(v.data_ptr());
+  auto* dop = reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr());
+  const float* lp = lse.data_ptr<float>();
+  const float* drp = drow.data_ptr<float>();
+  const int* dsp = doc_start.data_ptr<int>();
+  const int* dep = doc_end.data_ptr<int>();
+  auto launch = [&](auto dtag) {
+    constexpr int DD = decltype(dtag)::value;
+    attn_bwd_dq_kernel<DD, MOD_DOCUMENT, 8><<<gq, block, 0, stream>>>(
+        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()), nullptr,
+        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dq_rs,
+        nullptr, nullptr, nullptr, nullptr, dsp);
+    attn_bwd_dkv_kernel<DD, MOD_DOCUMENT, true, 8><<<gkv, block, 0, stream>>>(
+        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()), nullptr,
+        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dk_rs,
+        nullptr, nullptr, nullptr, nullptr, dep);
+    attn_bwd_dkv_kernel<DD, MOD_DOCUMENT, false, 8><<<gkv, block, 0, stream>>>(
+        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()), nullptr,
+        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dv_rs,
+        nullptr, nullptr, nullptr, nullptr, dep);
+  };
+  if (D == 64) launch(std::integral_constant<int, 64>{});
+  else launch(std::integral_constant<int, 128>{});
+  return {dq, dk, dv};
+}
+
+std::vector<at::Tensor> attn_bwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                     at::Tensor dout, at::Tensor lse, double scale,
+                                     at::Tensor doc_start, at::Tensor doc_end) {
+  auto none = at::empty({0}, q.options());
+  return attn_bwd_doc_out(q, k, v, o, dout, lse, scale, doc_start, doc_end,
+                          none, none.clone(), none.clone());
 }
 
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,

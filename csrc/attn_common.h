@@ -24,6 +24,16 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define MOD_PREFIX_LM 3
 #define MOD_ALIBI 4
 #define MOD_BLOCKMASK 5  // arbitrary mask_mod via device block-mask + packed bits
+// packed-sequence document mask: causal AND k_pos >= doc_start[b, q_pos].
+// Two int32 [B, S] tensors, shared by all heads, describe it: doc_start (first
+// position of the row's document; q-row-major kernels) and doc_end (one past
+// its last position; kv-row-major kernels). Training only: Sq == Skv.
+#define MOD_DOCUMENT 6
+
+// Values read from the document tensors are trusted in comparisons only;
+// anything that feeds an address or a loop bound goes through this first, so
+// an ill-formed tensor gives wrong numbers, never an out-of-range access.
+__device__ __forceinline__ int doc_clamp(int x, int s) { return min(max(x, 0), s); }
 
 __device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
   unsigned packed;

@@ -30,6 +30,9 @@
 //   - MOD_BLOCKMASK (K2): arbitrary mask_mod via device granule codes +
 //     packed keep-bits + per-block live kv ranges; optional additive bias
 //     stream for score_mod (ops/attention.py CompiledBlockMask),
+//   - MOD_DOCUMENT: packed-sequence document mask = causal plus a per-row
+//     lower bound read from one int32 [B,S] tensor; kv tiles in front of the
+//     block's first document are skipped (ops/attention.py document_bounds),
 //   - causal/sliding-window tiles skipped at block level; GQA reads the
 //     shared KV head directly; BSHD layout, strided views accepted.
 #include <torch/extension.h>
@@ -58,7 +61,12 @@ __global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
     const unsigned char* __restrict__ mb_gran = nullptr,
     const unsigned char* __restrict__ mb_bits = nullptr,
     const int* __restrict__ mb_range = nullptr,
-    const __hip_bfloat16* __restrict__ bias = nullptr) {
+    const __hip_bfloat16* __restrict__ bias = nullptr,
+    // MOD_DOCUMENT only: doc_start int32 [B,Sq], first position of each
+    // row's document (non-decreasing along s; same for every head)
+    const int* __restrict__ doc_start = nullptr) {
+  static_assert(MOD != MOD_DOCUMENT || (NW == 8 && VAR == 1),
+                "document mask: default NW/VAR instantiations only");
   constexpr int TPB = NW * WAVE;
   constexpr int QPB = NW * QPW;
   constexpr int DBLK = D / 16;  // QK^T d-slots
@@ -107,6 +115,14 @@ __global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
       qf[dblk] = u.v;
     }
   }
+  // document mask: this lane's lower bound, plus the wave's largest one (its
+  // last row's; wave-uniform load) for the mask-free test below
+  [[maybe_unused]] int dstart = 0, dstart_wmax = 0;
+  if constexpr (MOD == MOD_DOCUMENT) {
+    const int* ds = doc_start + (long)b * Sq;
+    dstart = ds[q_valid ? qrow : 0];
+    dstart_wmax = ds[__builtin_amdgcn_readfirstlane(min(q0w + QPW - 1, Sq - 1))];
+  }
 
   // ---- kv range ----
   const int blk_qpos_lo = qtile * QPB + q_off;
@@ -125,6 +141,10 @@ __global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
     kv_lo = r[0] * KVB;
     kv_hi = min(Skv, r[1] * KVB);
     if (kv_hi <= kv_lo) kv_hi = kv_lo;  // fully-masked row block: loop skips
+  } else if constexpr (MOD == MOD_DOCUMENT) {
+    // the block's first row has the smallest start (qtile*QPB < Sq by grid)
+    kv_hi = min(Skv, blk_qpos_hi + 1);
+    kv_lo = doc_clamp(doc_start[(long)b * Sq + qtile * QPB], Skv) & ~(KVB - 1);
   }
   const float slope2 = (MOD == MOD_ALIBI) ? slopes[hq] * LOG2E : 0.f;
   // blockmask strides (granule: this wave's 32-row q granule per kv tile)
@@ -272,6 +292,8 @@ __global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
       full = full && ((kv0 + KVB - 1 <= q0w + q_off) || (kv0 + KVB <= modarg));
     } else if constexpr (MOD == MOD_ALIBI) {
       full = false;  // slope term needs per-element positions anyway
+    } else if constexpr (MOD == MOD_DOCUMENT) {
+      full = full && (kv0 + KVB - 1 <= q0w + q_off) && (kv0 >= dstart_wmax);
     } else if constexpr (MOD == MOD_BLOCKMASK) {
       // per-wave granule: full only if every lane's granule says 2 AND no
       // bias (bias must be added per element)
@@ -306,6 +328,8 @@ __global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
             keep = q_valid && k_pos < Skv;
             if (keep)
               keep = (mb_bits[bits_row + (k_pos >> 3)] >> (k_pos & 7)) & 1;
+          } else if constexpr (MOD == MOD_DOCUMENT) {
+            keep = q_valid && k_pos < Skv && k_pos <= q_pos && k_pos >= dstart;
           } else {
             keep = q_valid && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
           }
@@ -572,6 +596,49 @@ std::vector<at::Tensor> attn_fwd_blockmask(at::Tensor q, at::Tensor k, at::Tenso
         nullptr, B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs,
         gran.data_ptr<unsigned char>(), bits.data_ptr<unsigned char>(),
         range.data_ptr<int>(), bp);
+  };
+  if (D == 64) launch1(std::integral_constant<int, 64>{});
+  else launch1(std::integral_constant<int, 128>{});
+  return {o, lse};
+}
+
+// Document-masked forward (packed sequences). doc_start int32 [B, S]: first
+// position of the document each row belongs to. Runs the default
+// configuration only (8 waves, KVB 128 at D=64 / 64 at D=128, VAR 1), so
+// MCDP_ATTN_NW / MCDP_ATTN_KVB / MCDP_ATTN_FWD_VAR do not apply here.
+std::vector<at::Tensor> attn_fwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
+                                     at::Tensor doc_start) {
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(), "attn_fwd_doc: GPU tensors only");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 &&
+              v.scalar_type() == at::kBFloat16, "attn_fwd_doc: bf16 only");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.sizes() == k.sizes(),
+              "attn_fwd_doc: q/k/v must be [B,S,H,D]");
+  const long q_rs = bshd_row_stride(q), k_rs = bshd_row_stride(k), v_rs = bshd_row_stride(v);
+  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
+  const int Skv = k.size(1), Hkv = k.size(2);
+  TORCH_CHECK(Sq == Skv, "attn_fwd_doc: document mask is training-only (Sq == Skv), got ",
+              Sq, " vs ", Skv);
+  TORCH_CHECK(k.size(0) == B && k.size(3) == D, "attn_fwd_doc: q/k shape mismatch");
+  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  TORCH_CHECK(D == 64 || D == 128, "attn_fwd_doc: head_dim must be 64 or 128, got ", D);
+  TORCH_CHECK(doc_start.scalar_type() == at::kInt && doc_start.is_contiguous() &&
+              doc_start.dim() == 2 && doc_start.size(0) == B && doc_start.size(1) == Sq &&
+              doc_start.device() == q.device(),
+              "attn_fwd_doc: doc_start must be contiguous int32 [B,S] on q's device");
+  auto o = at::empty({B, Sq, Hq, D}, q.options());
+  auto lse = at::empty({B, Hq, Sq}, q.options().dtype(at::kFloat));
+  auto stream = at::cuda::getCurrentHIPStream();
+  constexpr int QPB = 8 * QPW;
+  dim3 grid(cdiv(Sq, QPB), Hq, B), block(8 * WAVE);
+  auto launch1 = [&](auto dtag) {
+    constexpr int DD = decltype(dtag)::value;
+    attn_fwd_kernel<DD, MOD_DOCUMENT, 8, (DD == 64 ? 128 : 64), 1><<<grid, block, 0, stream>>>(
+        reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
+        reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
+        reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
+        reinterpret_cast<__hip_bfloat16*>(o.data_ptr()), lse.data_ptr<float>(),
+        nullptr, B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs,
+        nullptr, nullptr, nullptr, nullptr, doc_start.data_ptr<int>());
   };
   if (D == 64) launch1(std::integral_constant<int, 64>{});
   else launch1(std::integral_constant<int, 128>{});

@@ -57,6 +57,15 @@ std::vector<at::Tensor> attn_bwd_blockmask(at::Tensor q, at::Tensor k, at::Tenso
                                            double scale, at::Tensor gran, at::Tensor bits,
                                            at::Tensor range, at::Tensor qrange,
                                            at::Tensor bias);
+std::vector<at::Tensor> attn_fwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
+                                     at::Tensor doc_start);
+std::vector<at::Tensor> attn_bwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                     at::Tensor dout, at::Tensor lse, double scale,
+                                     at::Tensor doc_start, at::Tensor doc_end);
+std::vector<at::Tensor> attn_bwd_doc_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                         at::Tensor dout, at::Tensor lse, double scale,
+                                         at::Tensor doc_start, at::Tensor doc_end,
+                                         at::Tensor dq, at::Tensor dk, at::Tensor dv);
 // sampling.hip
 at::Tensor sample_token(at::Tensor logits, double temperature, double top_p, double min_p,
                         long seed);
@@ -117,6 +126,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flash attention backward into strided out views (fused dQKV)");
   m.def("attn_bwd_blockmask", &attn_bwd_blockmask,
         "backward of attn_fwd_blockmask (dq, dk, dv); bias gets no gradient");
+  m.def("attn_fwd_doc", &attn_fwd_doc,
+        "flash attention forward with a packed-sequence document mask (o, lse)");
+  m.def("attn_bwd_doc", &attn_bwd_doc, "backward of attn_fwd_doc (dq, dk, dv)");
+  m.def("attn_bwd_doc_out", &attn_bwd_doc_out,
+        "backward of attn_fwd_doc into strided out views (fused dQKV)");
   m.def("sample_token", &sample_token, "fused temperature/min-p sampling");
   m.def("sample_token_dev", &sample_token_dev,
         "graph-capturable sampling (device position salt)");

@@ -28,6 +28,7 @@ import torch
 
 from ..data import DataManager, TokenizerManager
 from ..models.llama import Model, ModelArgs
+from ..ops.attention import document_bounds
 from ..ops.cross_entropy import fused_cross_entropy
 from ..optim.enhanced import clip_by_global_norm, global_grad_norm
 from ..optim.flat_fused import FusedFlatAdamW
@@ -209,6 +210,15 @@ class Trainer:
                     + (" + sequence parallel" if self.sp else "")
                     + " (head/intermediate sharded, 1 all-reduce per sublayer)"
                 )
+        # data.preprocessing.document_mask: document-masked attention for
+        # packed rows (ops.attention.document_bounds + MOD_DOCUMENT kernels)
+        self.document_mask = bool(
+            (self.config.data.preprocessing or {}).get("document_mask", False))
+        if self.document_mask and self.sp:
+            raise ValueError(
+                "data.preprocessing.document_mask is not supported together with "
+                "system.sequence_parallel: the combination is untested; turn one of them off"
+            )
         self.logger.log_model_summary(self.model)
 
     def setup_training(self) -> None:
@@ -322,7 +332,14 @@ class Trainer:
                 )
             inputs = inputs[:, :mpe]
             targets = targets[:, :mpe]
-        logits = self.model(inputs)
+        if self.document_mask:
+            # packed rows: keep attention inside each document (training and
+            # validation alike); bounds follow the truncation above
+            doc_start, doc_end = document_bounds(
+                inputs, bos_id=self.tokenizer.BOS_TOKEN, eos_id=self.tokenizer.EOS_TOKEN)
+            logits = self.model(inputs, doc_start=doc_start, doc_end=doc_end)
+        else:
+            logits = self.model(inputs)
         vp0 = getattr(self.model, "_vp_vocab0", -1)
         if vp0 >= 0 and self.model.training:
             # vocab-parallel CE over the sharded lm head (parallel/tp.py):

@@ -160,7 +160,18 @@ class Attention(nn.Module):
         else:
             self.alibi_slopes = None
 
-    def forward(self, x: torch.Tensor, cache: Optional[KVCache] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, cache: Optional[KVCache] = None,
+                doc_start: Optional[torch.Tensor] = None,
+                doc_end: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if doc_start is not None:
+            # packed-sequence document mask (ops.attention.document_bounds):
+            # full-sequence training / evaluation forwards only
+            if cache is not None:
+                raise ValueError("document mask (doc_start) cannot be used with a KV cache "
+                                 "or static decode")
+            if self.flex_mask is not None:
+                raise ValueError("document mask (doc_start) cannot be combined with a "
+                                 "flex mask (Model.set_flex_mask)")
         if getattr(self, "_sp", False) and self.training:
             x = gather_sp(x)  # SP: S-sharded stream -> full sequence
         elif getattr(self, "_tp", False):
@@ -215,6 +226,7 @@ class Attention(nn.Module):
                 window=self.args.attention_window if atype == "flex" else None,
                 prefix_len=self.args.attention_prefix_len if atype == "flex" else None,
                 alibi_slopes=self.alibi_slopes if self.args.use_alibi else None,
+                doc_start=doc_start, doc_end=doc_end,
             )
             out = self.wo(o.reshape(B, S, -1))
             if getattr(self, "_sp", False) and self.training:
@@ -244,7 +256,7 @@ class Attention(nn.Module):
         atype = self.args.attention_type
         if atype == "simple":
             # reference SimpleAttention parity path (fp32 composition)
-            o = attention_ref(q, k, v, causal=True, scale=self.scale)
+            o = attention_ref(q, k, v, causal=True, scale=self.scale, doc_start=doc_start)
         else:
             o = flash_attention(
                 q, k, v,
@@ -431,13 +443,17 @@ class TransformerBlock(nn.Module):
         implement (/root/reference/core/training.py:584-618)."""
         self._checkpoint = True
 
-    def _inner(self, x: torch.Tensor, cache: Optional[KVCache]) -> torch.Tensor:
-        x = x + self.attention(self.attention_norm(x), cache)
+    def _inner(self, x: torch.Tensor, cache: Optional[KVCache],
+               doc_start: Optional[torch.Tensor] = None,
+               doc_end: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = x + self.attention(self.attention_norm(x), cache, doc_start, doc_end)
         x = x + self.mlp(self.mlp_norm(x))
         return x
 
     def _inner_pair(self, res: torch.Tensor, delta: Optional[torch.Tensor],
-                    cache: Optional[KVCache]):
+                    cache: Optional[KVCache],
+                    doc_start: Optional[torch.Tensor] = None,
+                    doc_end: Optional[torch.Tensor] = None):
         """Residual-fused path: the incoming stream is (res, delta) with
         x = res + delta; every residual add happens INSIDE the following
         RMSNorm kernel (ops.rmsnorm.add_rms_norm -> csrc/rmsnorm.hip
@@ -451,18 +467,23 @@ class TransformerBlock(nn.Module):
             x, y1 = add_rms_norm(res, delta, self.attention_norm.weight,
                                  self.attention_norm.eps,
                                  self.attention_norm.emit_amax)
-        a = self.attention(y1, cache)
+        a = self.attention(y1, cache, doc_start, doc_end)
         h, y2 = add_rms_norm(x, a, self.mlp_norm.weight, self.mlp_norm.eps,
                              self.mlp_norm.emit_amax)
         return h, self.mlp(y2)
 
     def forward_pair(self, res: torch.Tensor, delta: Optional[torch.Tensor],
-                     cache: Optional[KVCache] = None):
+                     cache: Optional[KVCache] = None,
+                     doc_start: Optional[torch.Tensor] = None,
+                     doc_end: Optional[torch.Tensor] = None):
+        # the document tensors travel as ARGUMENTS: checkpointing re-runs
+        # _inner_pair during backward and hands it the same arguments again
         if self._checkpoint and self.training and cache is None:
             return torch.utils.checkpoint.checkpoint(
-                self._inner_pair, res, delta, cache, use_reentrant=False
+                self._inner_pair, res, delta, cache, doc_start, doc_end,
+                use_reentrant=False
             )
-        return self._inner_pair(res, delta, cache)
+        return self._inner_pair(res, delta, cache, doc_start, doc_end)
 
     def _static_decode(self, x: torch.Tensor, cache) -> torch.Tensor:
         """hipGraph decode layer: fused GEMV chain (csrc/gemv.hip gemv_ex) —
@@ -485,7 +506,12 @@ class TransformerBlock(nn.Module):
         out = ext.gemv_ex(gu, self.mlp.w_down.weight, 2, none, 0.0, h)
         return out.view_as(x)
 
-    def forward(self, x: torch.Tensor, cache: Optional[KVCache] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, cache: Optional[KVCache] = None,
+                doc_start: Optional[torch.Tensor] = None,
+                doc_end: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if doc_start is not None and cache is not None:
+            raise ValueError("document mask (doc_start) cannot be used with a KV cache "
+                             "or static decode")
         if (
             getattr(cache, "static_decode", False)
             and x.is_cuda
@@ -496,9 +522,9 @@ class TransformerBlock(nn.Module):
             return self._static_decode(x[:, 0, :], cache).unsqueeze(1)
         if self._checkpoint and self.training and cache is None:
             return torch.utils.checkpoint.checkpoint(
-                self._inner, x, cache, use_reentrant=False
+                self._inner, x, cache, doc_start, doc_end, use_reentrant=False
             )
-        return self._inner(x, cache)
+        return self._inner(x, cache, doc_start, doc_end)
 
 
 class Model(nn.Module):
@@ -540,8 +566,20 @@ class Model(nn.Module):
             layer.attention.flex_mask = mask
 
     def forward(
-        self, tokens: torch.Tensor, cache: Optional[List[KVCache]] = None
+        self, tokens: torch.Tensor, cache: Optional[List[KVCache]] = None,
+        doc_start: Optional[torch.Tensor] = None,
+        doc_end: Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
+        """``doc_start`` / ``doc_end`` (int32 [B, S], ops.attention.
+        document_bounds): packed-sequence document mask for every layer —
+        each token attends inside its own document only. Full-sequence
+        forwards only (no cache); not combinable with set_flex_mask."""
+        if doc_start is None and doc_end is not None:
+            raise ValueError("doc_end needs doc_start")
+        if doc_start is not None and cache is not None:
+            # the cached loop below does not carry the tensors at all
+            raise ValueError("document mask (doc_start) cannot be used with a KV cache "
+                             "or static decode")
         vp0 = getattr(self, "_vp_vocab0", -1)
         vp_tied = vp0 >= 0 and self.args.tie_word_embeddings
         if vp_tied:
@@ -577,7 +615,8 @@ class Model(nn.Module):
             res, delta = x, None
             for i, layer in enumerate(self.layers):
                 res, delta = layer.forward_pair(
-                    res, delta, cache[i] if cache is not None else None
+                    res, delta, cache[i] if cache is not None else None,
+                    doc_start, doc_end,
                 )
             # MoE: surface the summed load-balance loss for the trainer
             aux = [layer.mlp.aux_loss for layer in self.layers

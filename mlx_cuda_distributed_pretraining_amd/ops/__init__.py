@@ -6,6 +6,7 @@ from .attention import (
     BlockMask,
     attention_ref,
     create_block_mask,
+    document_bounds,
     flash_attention,
     flex_attention,
 )
@@ -20,7 +21,8 @@ __all__ = [
     "RopeTable", "apply_rope", "rope_ref",
     "swiglu", "swiglu_ref",
     "fused_cross_entropy", "cross_entropy_ref",
-    "BlockMask", "attention_ref", "create_block_mask", "flash_attention", "flex_attention",
+    "BlockMask", "attention_ref", "create_block_mask", "document_bounds",
+    "flash_attention", "flex_attention",
     "make_sampler", "make_logits_processors", "sample_token",
     "FastLinear", "linear_fast", "fp8_linear", "quantize_e4m3",
     "fused_optim", "get_ext", "require_ext",

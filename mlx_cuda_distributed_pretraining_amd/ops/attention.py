@@ -52,10 +52,14 @@ def attention_ref(
     score_mod: Optional[Callable] = None,
     mask_mod: Optional[Callable] = None,
     return_lse: bool = False,
+    doc_start: Optional[torch.Tensor] = None,
 ):
     """fp32 reference composition (used on CPU and as the test oracle).
 
     q: [B, S, Hq, D]; k, v: [B, Skv, Hkv, D] (BSHD).
+    doc_start: optional int [B, S] document lower bounds (``document_bounds``):
+    row (b, s) additionally keeps only keys at positions >= doc_start[b, s].
+    It needs S == Skv and is combined with the other masks by AND.
     score_mod(scores[B,H,S,S], b_idx, h_idx, q_idx, kv_idx) -> scores, applied
     to the scaled scores (FlexAttention semantics, vectorized over the full
     score tensor). mask_mod(b, h, q_idx, kv_idx) -> bool keep-mask. Index
@@ -105,7 +109,15 @@ def attention_ref(
         b_idx = torch.arange(B, device=q.device)
         h_idx = torch.arange(Hq, device=q.device)
         keep = keep & mask_mod(b_idx, h_idx, q_idx, kv_idx)
-    scores = scores.masked_fill(~keep.view(1, 1, S, Skv), float("-inf"))
+    keep = keep.view(1, 1, S, Skv)
+    if doc_start is not None:
+        if S != Skv or tuple(doc_start.shape) != (B, S):
+            raise ValueError(
+                f"doc_start must be [B, S] = [{B}, {S}] with Sq == Skv, got "
+                f"{tuple(doc_start.shape)} (Skv = {Skv})")
+        # batch-dependent: the keep mask becomes [B, 1, S, Skv]
+        keep = keep & (kv_idx.view(1, 1, 1, Skv) >= doc_start.view(B, 1, S, 1))
+    scores = scores.masked_fill(~keep, float("-inf"))
     lse = torch.logsumexp(scores, dim=-1)
     p = torch.softmax(scores, dim=-1)
     # rows with no valid keys produce NaN from softmax over all -inf; zero them
@@ -116,10 +128,94 @@ def attention_ref(
     return o.to(q.dtype).contiguous()
 
 
+def _doc_end_from_starts(is_start: torch.Tensor) -> torch.Tensor:
+    """is_start bool [B, S] -> int32 [B, S]: the next start after each column
+    (S when there is none), i.e. one past the column's document."""
+    B, S = is_start.shape
+    idx = torch.arange(S, device=is_start.device).expand(B, S)
+    nxt = torch.where(is_start, idx, torch.full_like(idx, S))
+    # suffix minimum = flip-cummin; column s wants the minimum over t > s
+    sfx = torch.cummin(nxt.flip(1), dim=1).values.flip(1)
+    end = torch.cat([sfx[:, 1:], torch.full_like(idx[:, :1], S)], dim=1)
+    return end.to(torch.int32).contiguous()
+
+
+def document_bounds(tokens: torch.Tensor, bos_id: Optional[int] = None,
+                    eos_id: Optional[int] = None):
+    """Document bounds of packed token rows, for document-masked attention.
+
+    tokens: int [B, S]. A document starts at column 0, at every ``bos_id`` and
+    right after every ``eos_id`` (an ``EOS BOS`` pair therefore opens one
+    document, not two). Returns ``(doc_start, doc_end)``, both int32 [B, S] on
+    the tokens' device: the first position of each column's document and one
+    past its last. Both are non-decreasing along S and
+    ``doc_start[b, s] <= s < doc_end[b, s]``. A few vectorised ops, no host
+    sync, no Python loop over B or S.
+    """
+    if tokens.dim() != 2:
+        raise ValueError(f"document_bounds wants [B, S] tokens, got {tuple(tokens.shape)}")
+    B, S = tokens.shape
+    is_start = torch.zeros(B, S, dtype=torch.bool, device=tokens.device)
+    is_start[:, :1] = True
+    if bos_id is not None:
+        is_start |= tokens == bos_id
+    if eos_id is not None:
+        is_start[:, 1:] |= tokens[:, :-1] == eos_id
+    idx = torch.arange(S, device=tokens.device).expand(B, S)
+    start = torch.cummax(torch.where(is_start, idx, torch.zeros_like(idx)), dim=1).values
+    return start.to(torch.int32).contiguous(), _doc_end_from_starts(is_start)
+
+
+def _doc_pair(doc_start, doc_end, B: int, S: int, device):
+    """Normalise the document tensors for the kernels: int32, contiguous,
+    [B, S], on ``device``; doc_end derived from doc_start when omitted (column
+    s opens a document exactly when doc_start[b, s] == s)."""
+    if tuple(doc_start.shape) != (B, S):
+        raise ValueError(f"doc_start must be [B, S] = [{B}, {S}], got {tuple(doc_start.shape)}")
+    doc_start = doc_start.to(device=device, dtype=torch.int32).contiguous()
+    if doc_end is None:
+        idx = torch.arange(S, device=device, dtype=torch.int32)
+        doc_end = _doc_end_from_starts(doc_start == idx)
+    else:
+        if tuple(doc_end.shape) != (B, S):
+            raise ValueError(f"doc_end must be [B, S] = [{B}, {S}], got {tuple(doc_end.shape)}")
+        doc_end = doc_end.to(device=device, dtype=torch.int32).contiguous()
+    return doc_start, doc_end
+
+
+def _check_doc_args(doc_start, doc_end, causal, window, prefix_len, alibi_slopes, Sq, Skv):
+    if doc_start is None:
+        if doc_end is not None:
+            raise ValueError("doc_end needs doc_start")
+        return
+    if window is not None or prefix_len is not None or alibi_slopes is not None:
+        raise ValueError("document mask (doc_start) cannot be combined with "
+                         "window, prefix_len or ALiBi")
+    if not causal:
+        raise ValueError("document mask (doc_start) is causal: causal=False is not supported")
+    if Sq != Skv:
+        raise ValueError(f"document mask (doc_start) is training-only: Sq ({Sq}) != Skv ({Skv})")
+
+
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, window, prefix_len, alibi_slopes):
+    def forward(ctx, q, k, v, causal, scale, window, prefix_len, alibi_slopes,
+                doc_start=None, doc_end=None):
         scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+        if doc_start is not None:
+            # document mask: attn_fwd_doc / attn_bwd_doc on the kernel path,
+            # the fp32 composition otherwise (argument checks: flash_attention)
+            hip = use_hip(q, k, v, dtypes=(torch.bfloat16,))
+            if hip:
+                o, lse = get_ext().attn_fwd_doc(q, k, v, scale, doc_start)
+            else:
+                o, lse = attention_ref(q, k, v, causal=True, scale=scale,
+                                       return_lse=True, doc_start=doc_start)
+            ctx.save_for_backward(q, k, v, o, lse, doc_start, doc_end)
+            ctx.meta = (scale, hip)
+            ctx.doc = True
+            return o
+        ctx.doc = False
         if use_hip(q, k, v, dtypes=(torch.bfloat16,)):
             ext = get_ext()
             mod = _mods_to_code(causal, window, prefix_len, alibi_slopes is not None)
@@ -152,6 +248,20 @@ class _FlashAttnFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
+        if ctx.doc:
+            q, k, v, o, lse, doc_start, doc_end = ctx.saved_tensors
+            scale, hip = ctx.meta
+            if hip:
+                dq, dk, dv = get_ext().attn_bwd_doc(q, k, v, o, do, lse, scale,
+                                                    doc_start, doc_end)
+                return (dq, dk, dv) + (None,) * 7
+            with torch.enable_grad():
+                qf = q.detach().float().requires_grad_(True)
+                kf = k.detach().float().requires_grad_(True)
+                vf = v.detach().float().requires_grad_(True)
+                of = attention_ref(qf, kf, vf, causal=True, scale=scale, doc_start=doc_start)
+                grads = torch.autograd.grad(of, [qf, kf, vf], do.float())
+            return (grads[0].to(q.dtype), grads[1].to(k.dtype), grads[2].to(v.dtype)) + (None,) * 7
         q, k, v, o, lse, slopes = ctx.saved_tensors
         causal, scale, window, prefix_len, hip = ctx.meta
         if hip:
@@ -161,7 +271,7 @@ class _FlashAttnFn(torch.autograd.Function):
                 window if window is not None else (prefix_len if prefix_len is not None else 0)
             )
             dq, dk, dv = ext.attn_bwd(q, k, v, o, do, lse, scale, mod, modarg, slopes)
-            return dq, dk, dv, None, None, None, None, None
+            return (dq, dk, dv) + (None,) * 7
         # CPU reference backward: recompute with autograd in fp32
         with torch.enable_grad():
             qf = q.detach().float().requires_grad_(True)
@@ -175,7 +285,7 @@ class _FlashAttnFn(torch.autograd.Function):
             grads = torch.autograd.grad(of, [qf, kf, vf], do.float())
         return (
             grads[0].to(q.dtype), grads[1].to(k.dtype), grads[2].to(v.dtype),
-            None, None, None, None, None,
+            None, None, None, None, None, None, None,
         )
 
 
@@ -199,10 +309,43 @@ def flash_attention(
     window: Optional[int] = None,
     prefix_len: Optional[int] = None,
     alibi_slopes: Optional[torch.Tensor] = None,
+    doc_start: Optional[torch.Tensor] = None,
+    doc_end: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Tiled attention, BSHD layout: [B,S,Hq,D] x [B,S,Hkv,D] -> [B,S,Hq,D]
-    (q.shape[2] is the HEAD count — _norm_alibi relies on that)."""
+    (q.shape[2] is the HEAD count — _norm_alibi relies on that).
+
+    Document mask (packed sequences)
+    --------------------------------
+    ``doc_start`` / ``doc_end`` (int [B, S], from ``document_bounds``) keep
+    every token inside its own document: row (b, s) attends to keys in
+    ``[doc_start[b, s], s]``. The mask is the same for all heads, costs two
+    int32 rows per sequence instead of S^2 bits per head, and is rebuilt per
+    batch with a few device ops. On bf16 GPU inputs it runs the MOD_DOCUMENT
+    kernels forward and backward (csrc/attn_fwd.hip, csrc/attn_bwd.hip), which
+    skip the kv tiles in front of a q block's first document and the q tiles
+    past a kv block's last one, so it does no more work than causal. CPU and
+    other dtypes run ``attention_ref(doc_start=...)``.
+
+      * ``doc_end`` is derived from ``doc_start`` when omitted.
+      * Training only: it needs Sq == Skv and ``causal=True``, and cannot be
+        combined with ``window``, ``prefix_len`` or ALiBi (``ValueError``).
+      * Both tensors must be well-formed (non-decreasing,
+        ``doc_start <= s < doc_end``); the kernels clamp what they use as an
+        address or loop bound, so a bad tensor gives wrong numbers, not a
+        fault.
+      * The kernel path is built for the default launch configuration only:
+        MCDP_ATTN_NW, MCDP_ATTN_KVB, MCDP_ATTN_FWD_VAR and MCDP_ATTN_BWD_NW
+        do not apply to it.
+      * RoPE needs no per-document position reset: scores depend on
+        q_pos - k_pos only.
+    """
     alibi_slopes = _norm_alibi(alibi_slopes, q.shape[2], q.device)
+    _check_doc_args(doc_start, doc_end, causal, window, prefix_len, alibi_slopes,
+                    q.shape[1], k.shape[1])
+    if doc_start is not None:
+        doc_start, doc_end = _doc_pair(doc_start, doc_end, q.shape[0], q.shape[1], q.device)
+        return _FlashAttnFn.apply(q, k, v, True, scale, None, None, None, doc_start, doc_end)
     return _FlashAttnFn.apply(q, k, v, causal, scale, window, prefix_len, alibi_slopes)
 
 
@@ -217,7 +360,7 @@ class _RopeAttnQKVFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, cos, sin, Hq, Hkv, D, traditional, causal, scale,
-                window, prefix_len, alibi_slopes):
+                window, prefix_len, alibi_slopes, doc_start=None, doc_end=None):
         B, S, _ = qkv.shape
         scale = scale if scale is not None else 1.0 / math.sqrt(D)
         q = qkv[..., : Hq * D].view(B, S, Hq, D)
@@ -231,14 +374,20 @@ class _RopeAttnQKVFn(torch.autograd.Function):
                      else (prefix_len if prefix_len is not None else 0))
         slopes = (alibi_slopes.float().contiguous() if alibi_slopes is not None
                   else torch.empty(0, dtype=torch.float32, device=qkv.device))
-        o, lse = ext.attn_fwd(qr, kr, v, scale, mod, modarg, slopes)
-        ctx.save_for_backward(qkv, qr, kr, o, lse, cos, sin, slopes)
+        ctx.doc = doc_start is not None
+        if ctx.doc:
+            # document mask (argument checks: rope_flash_attention_qkv)
+            o, lse = ext.attn_fwd_doc(qr, kr, v, scale, doc_start)
+            ctx.save_for_backward(qkv, qr, kr, o, lse, cos, sin, slopes, doc_start, doc_end)
+        else:
+            o, lse = ext.attn_fwd(qr, kr, v, scale, mod, modarg, slopes)
+            ctx.save_for_backward(qkv, qr, kr, o, lse, cos, sin, slopes)
         ctx.meta = (Hq, Hkv, D, traditional, scale, mod, modarg)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, qr, kr, o, lse, cos, sin, slopes = ctx.saved_tensors
+        qkv, qr, kr, o, lse, cos, sin, slopes = ctx.saved_tensors[:8]
         Hq, Hkv, D, traditional, scale, mod, modarg = ctx.meta
         B, S, _ = qkv.shape
         ext = get_ext()
@@ -248,11 +397,16 @@ class _RopeAttnQKVFn(torch.autograd.Function):
         dk_t = dqkv[..., Hq * D : (Hq + Hkv) * D].view(B, S, Hkv, D)
         dv_t = dqkv[..., (Hq + Hkv) * D :].view(B, S, Hkv, D)
         none = torch.empty(0, dtype=qkv.dtype, device=qkv.device)
-        dq_r, dk_r, _ = ext.attn_bwd_out(qr, kr, v, o, do, lse, scale, mod,
-                                         modarg, slopes, none, none.clone(), dv_t)
+        if ctx.doc:
+            doc_start, doc_end = ctx.saved_tensors[8:]
+            dq_r, dk_r, _ = ext.attn_bwd_doc_out(qr, kr, v, o, do, lse, scale, doc_start,
+                                                 doc_end, none, none.clone(), dv_t)
+        else:
+            dq_r, dk_r, _ = ext.attn_bwd_out(qr, kr, v, o, do, lse, scale, mod,
+                                             modarg, slopes, none, none.clone(), dv_t)
         ext.rope_fwd_out(dq_r, cos, sin, traditional, 0, True, dq_t)
         ext.rope_fwd_out(dk_r, cos, sin, traditional, 0, True, dk_t)
-        return (dqkv,) + (None,) * 11
+        return (dqkv,) + (None,) * 13
 
 
 def rope_flash_attention_qkv(
@@ -268,25 +422,32 @@ def rope_flash_attention_qkv(
     window: Optional[int] = None,
     prefix_len: Optional[int] = None,
     alibi_slopes: Optional[torch.Tensor] = None,
+    doc_start: Optional[torch.Tensor] = None,
+    doc_end: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """qkv: [B, S, (Hq+2*Hkv)*D] fused projection output -> o [B, S, Hq, D].
 
     HIP fast path (one fused autograd node, no grad cat); CPU falls back to
-    the differentiable composition of the same ops."""
+    the differentiable composition of the same ops. ``doc_start`` /
+    ``doc_end``: packed-sequence document mask, see ``flash_attention``."""
+    B, S, _ = qkv.shape
+    _check_doc_args(doc_start, doc_end, causal, window, prefix_len, alibi_slopes, S, S)
     if use_hip(qkv, dtypes=(torch.bfloat16,)):
+        if doc_start is not None:
+            doc_start, doc_end = _doc_pair(doc_start, doc_end, B, S, qkv.device)
         return _RopeAttnQKVFn.apply(qkv, cos, sin, n_heads, n_kv_heads, head_dim,
                                     traditional, causal, scale, window,
-                                    prefix_len, alibi_slopes)
+                                    prefix_len, alibi_slopes, doc_start, doc_end)
     from .rope import apply_rope
 
-    B, S, _ = qkv.shape
     Hq, Hkv, D = n_heads, n_kv_heads, head_dim
     q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
     q = apply_rope(q.view(B, S, Hq, D), cos, sin, traditional, 0)
     k = apply_rope(k.view(B, S, Hkv, D), cos, sin, traditional, 0)
     return flash_attention(q, k, v.view(B, S, Hkv, D), causal=causal, scale=scale,
                            window=window, prefix_len=prefix_len,
-                           alibi_slopes=alibi_slopes)
+                           alibi_slopes=alibi_slopes, doc_start=doc_start,
+                           doc_end=doc_end)
 
 
 def flex_attention(
