@@ -1,14 +1,25 @@
 // Tiled FlashAttention-2 backward (kernel K1 bwd).
 //
-// Deterministic three-kernel design (no atomics):
-//   preprocess: Drow[b,h,s] = sum_d dO*O  (vectorized 16B loads, 4 rows/wave)
-//   dQ kernel : block per q-tile; recomputes P from (Q,K,lse); accumulates
-//               dQ = (P∘(dP−Drow))·scale @ K in registers
-//   dK kernel : block per kv-tile; loops the GQA group's q heads; accumulates
-//               dK = dS^T @ Q in registers
-//   dV kernel : block per kv-tile; accumulates dV = P^T @ dO in registers
-// Splitting dK/dV keeps each kernel under the 256-VGPR budget at D=128
-// (merged, the two 32x128 fp32 accumulators alone are 128 VGPRs).
+// Deterministic design (no atomics):
+//   preprocess  : Drow[b,h,s] = sum_d dO*O  (vectorized 16B loads, 4 rows/wave)
+//   dQ kernel   : block per q-tile; recomputes P from (Q,K,lse); accumulates
+//                 dQ = (P∘(dP−Drow))·scale @ K in registers
+//   dK+dV kernel: block per kv-tile; loops the GQA group's q heads ONCE and
+//                 accumulates both dK = dS^T @ Q and dV = P^T @ dO
+//                 (attn_bwd_dkdv_kernel: D=128, 8 waves/block, every mod but
+//                 blockmask). The two 32x128 fp32 accumulators are 128 VGPRs;
+//                 it fits the 256-VGPR budget because the K and V fragments
+//                 live in a wave-private LDS image instead of 64 registers.
+//   dK kernel / dV kernel (attn_bwd_dkv_kernel): the split pair the merged
+//                 kernel replaced — each streams the same Q and dO tiles and
+//                 recomputes the same S and P. Still the path for D=64 (both
+//                 fit registers there at 2-3 waves/SIMD, not ported), for
+//                 NW != 8, for the blockmask entry point (not ported: its
+//                 bits / bias addressing wants registers the merged kernel
+//                 does not have to spare without a re-tune) and under
+//                 MCDP_ATTN_BWD_SPLIT=1; attn_bwd_split always runs
+//                 it. Both paths share bwd_p_ds_tile, and their dK and dV
+//                 are bit-identical (tests/test_gpu_attn_bwd_merged.py).
 //
 // Same gfx950 structure as the forward (attn_fwd.hip): 8 waves/block sharing
 // every staged tile, DOUBLE-BUFFERED tiles with one barrier per iteration,
@@ -45,6 +56,16 @@ inline int bwd_nw() {
     return e ? atoi(e) : 8;
   }();
   return nw;
+}
+
+// MCDP_ATTN_BWD_SPLIT=1: run the split dK and dV kernels where the merged
+// dK+dV kernel is the default (D=128, 8 waves/block).
+inline bool bwd_split() {
+  static bool split = []() {
+    const char* e = getenv("MCDP_ATTN_BWD_SPLIT");
+    return e != nullptr && atoi(e) != 0;
+  }();
+  return split;
 }
 
 // ---------------- preprocess: Drow = rowsum(dO * O) ----------------
@@ -417,7 +438,72 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
   }
 }
 
+// ---------------- P / dS of one 32x32 (q, k) tile, kv-row-major kernels ------
+// The one per-element body of the split dK / dV kernels and of the merged
+// dK+dV kernel, so all three form p and dS by the same arithmetic (the merged
+// results are required to be bit-identical to the split ones).
+//   s_acc / dp_acc : S and dP accumulators, element (r=q_local, c=k_local)
+//   Ls / Ds        : LDS stats of the tile's 32 q rows (lse*log2e, Drow)
+//   full           : wave-uniform, every element of the tile is kept
+//   pv  <- p                        (WANT_P)
+//   dsv <- p * (dP - Drow) * scale  (WANT_DS)
+template <int MOD, bool WANT_P, bool WANT_DS>
+__device__ __forceinline__ void bwd_p_ds_tile(
+    const f32x16& s_acc, const f32x16& dp_acc, const float* Ls, const float* Ds,
+    bool full, int hi, int q0, int q_off, int krow, bool k_valid, int Sq, int Skv,
+    int modarg, float scale, float scale2, float slope2,
+    // MOD_DOCUMENT: this lane's doc end; MOD_BLOCKMASK: bits / bias planes and
+    // the (b, q head) plane index
+    int dend, const unsigned char* mb_bits, const __hip_bfloat16* bias, long bh, int kvb8,
+    float (&pv)[16], float (&dsv)[16]) {
+  if (full) {
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int qr = acc_row(reg, hi);
+      const float p = __builtin_amdgcn_exp2f(s_acc[reg] * scale2 - Ls[qr]);
+      if constexpr (WANT_P) pv[reg] = p;
+      if constexpr (WANT_DS) dsv[reg] = p * (dp_acc[reg] - Ds[qr]) * scale;
+    }
+  } else {
+    // blockmask: the lane holds ONE k column and 16 q rows, so its
+    // keep bits sit in 16 different bits rows (partial granules only)
+    [[maybe_unused]] const unsigned char* bits_h = nullptr;
+    [[maybe_unused]] const __hip_bfloat16* bias_h = nullptr;
+    if constexpr (MOD == MOD_BLOCKMASK) {
+      bits_h = mb_bits + bh * Sq * (long)kvb8 + (krow >> 3);
+      if (bias != nullptr) bias_h = bias + bh * Sq * (long)Skv + krow;
+    }
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int qr = acc_row(reg, hi);
+      const int q_r = q0 + qr;
+      const int q_pos = q_r + q_off;
+      const int k_pos = krow;
+      bool keep;
+      if constexpr (MOD == MOD_BLOCKMASK) {
+        keep = k_valid && q_r < Sq;
+        if (keep) keep = (bits_h[(long)q_r * kvb8] >> (krow & 7)) & 1;
+      } else if constexpr (MOD == MOD_DOCUMENT) {
+        keep = q_r < Sq && k_valid && q_r >= krow && q_r < dend;
+      } else {
+        keep = k_valid && q_r < Sq && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
+      }
+      float s2 = s_acc[reg] * scale2;
+      if constexpr (MOD == MOD_ALIBI) s2 += slope2 * (k_pos - q_pos);
+      if constexpr (MOD == MOD_BLOCKMASK) {
+        if (bias != nullptr && keep)
+          s2 += __bfloat162float(bias_h[(long)q_r * Skv]) * LOG2E;
+      }
+      const float p = keep ? __builtin_amdgcn_exp2f(s2 - Ls[qr]) : 0.f;
+      if constexpr (WANT_P) pv[reg] = p;
+      if constexpr (WANT_DS) dsv[reg] = p * (dp_acc[reg] - Ds[qr]) * scale;
+    }
+  }
+}
+
 // ---------------- dK / dV kernels (block per kv-tile, loop GQA group) -------
+// The split pair: the path for D=64, NW != 8, the blockmask entry point and
+// MCDP_ATTN_BWD_SPLIT=1; everything else runs the merged kernel below.
 // WANT_DK: true -> dK (needs dP: V frags + dO rm); false -> dV (needs dO^T).
 template <int D, int MOD, bool WANT_DK, int NW>
 __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
@@ -547,8 +633,17 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
   constexpr int NU = (2 * CH_TOT + TPB - 1) / TPB;
   uint4 sreg[NU][2];  // ONE sub-tile's chunk pairs at a time (split-half
                       // staging: load s -> compute s-1 -> write s)
+  // the sub-tile's lse / Drow ride the same pipeline in lanes 0-31 of wave 0:
+  // loaded next to the tile, stored to LDS with it, so their latency hides
+  // under the compute like the tile's instead of sitting before the barrier
+  float st_l = 0.f, st_d = 0.f;
 
   auto stage_load = [&](int hq_, int q0) {
+    if (tid < 32) {
+      const int qr = q0 + tid;
+      st_l = (qr < Sq) ? lse[((long)b * Hq + hq_) * Sq + qr] : INFINITY;
+      st_d = (qr < Sq) ? drow[((long)b * Sq + qr) * Hq + hq_] : 0.f;
+    }
 #pragma unroll
     for (int cu = 0; cu < NU; ++cu) {
       const int u0 = tid + cu * TPB;
@@ -581,6 +676,10 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
       *reinterpret_cast<uint4*>(dst + rm_swz<D>(row, d0)) = sreg[cu][0];
       *reinterpret_cast<uint4*>(dst + rm_swz<D>(row + 1, d0)) = sreg[cu][1];
     }
+    if (tid < 32) {
+      stats_lds[bufsel][0][s * 32 + tid] = st_l * LOG2E;
+      stats_lds[bufsel][1][s * 32 + tid] = st_d;
+    }
   };
 
   // iterate (GQA head, q tile) pairs with a flat prefetch pipeline
@@ -593,26 +692,15 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
       hq_ = hkv * group + it / ntiles;
       q0 = q_lo + (it % ntiles) * 32;
     };
-    auto load_stats = [&](int bufsel, int s, int hq_, int q0) {
-      if (tid < 32) {
-        const int qr = q0 + tid;
-        stats_lds[bufsel][0][s * 32 + tid] =
-            ((qr < Sq) ? lse[((long)b * Hq + hq_) * Sq + qr] : INFINITY) * LOG2E;
-        stats_lds[bufsel][1][s * 32 + tid] =
-            (qr < Sq) ? drow[((long)b * Sq + qr) * Hq + hq_] : 0.f;
-      }
-    };
     int hq0_, q00;
     iter_to(0, hq0_, q00);
     stage_load(hq0_, q00);
     stage_write(0, 0);
-    load_stats(0, 0, hq0_, q00);
     if (NP == 2 && total_iters > 1) {
       int hq1_, q01;
       iter_to(1, hq1_, q01);
       stage_load(hq1_, q01);
       stage_write(0, 1);
-      load_stats(0, 1, hq1_, q01);
     }
     __syncthreads();
 
@@ -694,58 +782,12 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
             full = false;  // MOD_NONE boundary Sq checks + ALIBI slope
           }
 
-          float pv[16];
-          if (full) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-              const int qr = s * 32 + acc_row(reg, hi);
-              const float p = __builtin_amdgcn_exp2f(s_acc[reg] * scale2 - stats_lds[buf][0][qr]);
-              if constexpr (WANT_DK) {
-                pv[reg] = p * (dp_acc[reg] - stats_lds[buf][1][qr]) * scale;  // dS
-              } else {
-                pv[reg] = p;
-              }
-            }
-          } else {
-            // blockmask: the lane holds ONE k column and 16 q rows, so its
-            // keep bits sit in 16 different bits rows (partial granules only)
-            [[maybe_unused]] const unsigned char* bits_h = nullptr;
-            [[maybe_unused]] const __hip_bfloat16* bias_h = nullptr;
-            if constexpr (MOD == MOD_BLOCKMASK) {
-              const long bh = (long)b * Hq + hq_;
-              bits_h = mb_bits + bh * Sq * (long)kvb8 + (krow >> 3);
-              if (bias != nullptr) bias_h = bias + bh * Sq * (long)Skv + krow;
-            }
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-              const int qr = acc_row(reg, hi);
-              const int q_r = q0 + qr;
-              const int q_pos = q_r + q_off;
-              const int k_pos = krow;
-              bool keep;
-              if constexpr (MOD == MOD_BLOCKMASK) {
-                keep = k_valid && q_r < Sq;
-                if (keep) keep = (bits_h[(long)q_r * kvb8] >> (krow & 7)) & 1;
-              } else if constexpr (MOD == MOD_DOCUMENT) {
-                keep = q_r < Sq && k_valid && q_r >= krow && q_r < dend;
-              } else {
-                keep = k_valid && q_r < Sq && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
-              }
-              float s2 = s_acc[reg] * scale2;
-              if constexpr (MOD == MOD_ALIBI) s2 += slope2 * (k_pos - q_pos);
-              if constexpr (MOD == MOD_BLOCKMASK) {
-                if (bias != nullptr && keep)
-                  s2 += __bfloat162float(bias_h[(long)q_r * Skv]) * LOG2E;
-              }
-              const float p =
-                  keep ? __builtin_amdgcn_exp2f(s2 - stats_lds[buf][0][s * 32 + qr]) : 0.f;
-              if constexpr (WANT_DK) {
-                pv[reg] = p * (dp_acc[reg] - stats_lds[buf][1][s * 32 + qr]) * scale;  // dS
-              } else {
-                pv[reg] = p;
-              }
-            }
-          }
+          // dS (dK) or P (dV) of the tile; the other array stays unused
+          float pv[16], pv_unused[16];
+          bwd_p_ds_tile<MOD, !WANT_DK, WANT_DK>(
+              s_acc, dp_acc, &stats_lds[buf][0][s * 32], &stats_lds[buf][1][s * 32], full, hi,
+              q0, q_off, krow, k_valid, Sq, Skv, modarg, scale, scale2, slope2, dend, mb_bits,
+              bias, (long)b * Hq + hq_, kvb8, WANT_DK ? pv_unused : pv, WANT_DK ? pv : pv_unused);
 
           // transform: acc holds M[r=q][c=k]; A-frags of M^T = dS^T (dK) / P^T (dV)
           bf16x8 a0, a1;
@@ -772,19 +814,15 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
         // split-half staging epilogue: write the half that loaded during
         // this half's compute, then start the next half's load
         if (has_next) {
-          int nhq, nq0;
           if (s == 0) {
-            iter_to(it0 + NP, nhq, nq0);
             stage_write(buf ^ 1, 0);
-            load_stats(buf ^ 1, 0, nhq, nq0);
             if (NP == 2 && nleft > 1) {
+              int nhq, nq0;
               iter_to(it0 + NP + 1, nhq, nq0);
               stage_load(nhq, nq0);
             }
           } else if (nleft > 1) {
-            iter_to(it0 + NP + 1, nhq, nq0);
             stage_write(buf ^ 1, 1);
-            load_stats(buf ^ 1, 1, nhq, nq0);
           }
         }
       }
@@ -810,6 +848,305 @@ store:
   }
 }
 
+// ---------------- merged dK + dV kernel (block per kv-tile) -----------------
+// One pass over the (GQA head, q tile) sequence of the split kernels, in the
+// same order, with BOTH 32x128 fp32 accumulators per wave (128 VGPRs): Q and
+// dO are staged once, S and P are formed once, one barrier per q tile.
+// What makes it fit 256 VGPRs: the K and V fragments (64 registers in the
+// split dK kernel) live in a wave-private LDS image instead, written once in
+// the prologue in fragment order [dblk][lane] x 16 B — no other wave reads a
+// wave's 32 rows, so no swizzle is needed and each ds_read_b128 is one
+// contiguous 1 KB. The last K dblk stays in 4 registers, which is what keeps
+// the static LDS under the 160 KB limit:
+//   Q/dO tiles 2 x 16 KB + K image 8 x 7 KB + V image 8 x 8 KB + stats 512 B.
+// p and dS come from bwd_p_ds_tile and each accumulator sees its MFMAs in
+// the split kernels' order, so dK and dV are bit-identical to theirs.
+template <int D, int MOD>
+__global__ __launch_bounds__(8 * WAVE) void attn_bwd_dkdv_kernel(
+    const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
+    const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ drow,
+    __hip_bfloat16* __restrict__ dk_out, __hip_bfloat16* __restrict__ dv_out,
+    const float* __restrict__ slopes,
+    int B, int Sq, int Skv, int Hq, int Hkv, float scale, int modarg,
+    long q_rs, long k_rs, long v_rs, long do_rs, long dk_rs, long dv_rs,
+    // MOD_DOCUMENT only: doc_end int32 [B,Skv], as in the split kernels
+    const int* __restrict__ doc_end = nullptr) {
+  static_assert(D == 128, "merged dK+dV kernel is built for D=128");
+  static_assert(MOD != MOD_BLOCKMASK, "blockmask stays on the split kernels");
+  constexpr int NW = 8;
+  constexpr int TPB = NW * WAVE;
+  constexpr int KPB = 32 * NW;
+  constexpr int DBLK = D / 16;
+  constexpr int DCOL = D / 32;
+  constexpr int TILE = 2 * 32 * D;         // one 32-row Q tile + one 32-row dO tile
+  constexpr int FRAG = WAVE * 8;           // elements of one [lane] x 16 B fragment block
+  constexpr int KIMG = (DBLK - 1) * FRAG;  // per-wave K image (last dblk in registers)
+  constexpr int WIMG = KIMG + DBLK * FRAG; // per-wave K image + V image
+
+  __shared__ __align__(16) __hip_bfloat16 smem[2 * TILE + NW * WIMG];
+  __shared__ float stats_lds[2][2][32];  // [buf][L|D][qrow]
+  static_assert(sizeof(smem) + sizeof(stats_lds) <= 160 * 1024, "LDS budget");
+
+  const TileMap tmap = tile_map();
+  const int b = tmap.batch, hkv = tmap.head, kvtile = tmap.tile;
+  const int group = Hq / Hkv;
+  const int tid = threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
+  const int lk = lane & 31, hi = lane >> 5;
+  const int kv0w = kvtile * KPB + wave * 32;
+  const int krow = kv0w + lk;
+  const bool k_valid = krow < Skv;
+  const int q_off = Skv - Sq;
+  const float scale2 = scale * LOG2E;
+
+  // K / V fragments (lane holds row k=lk, 8 d values; rows past Skv are
+  // zeros) -> this wave's image. Only this wave reads it back, and the first
+  // barrier below sits between these writes and the first read anyway.
+  __hip_bfloat16* const kimg = smem + 2 * TILE + wave * WIMG + lane * 8;
+  __hip_bfloat16* const vimg = kimg + KIMG;
+  bf16x8 kf_last;
+  {
+    const long kr0 = (long)b * Skv + (k_valid ? krow : 0);
+    const long khd = (long)hkv * D + hi * 8;
+#pragma unroll
+    for (int dblk = 0; dblk < DBLK; ++dblk) {
+      Bf16x8U ku, vu;
+      *reinterpret_cast<uint4*>(ku.s) =
+          k_valid ? *reinterpret_cast<const uint4*>(k + kr0 * k_rs + khd + dblk * 16) : uint4{0, 0, 0, 0};
+      *reinterpret_cast<uint4*>(vu.s) =
+          k_valid ? *reinterpret_cast<const uint4*>(v + kr0 * v_rs + khd + dblk * 16) : uint4{0, 0, 0, 0};
+      if (dblk < DBLK - 1)
+        *reinterpret_cast<uint4*>(kimg + dblk * FRAG) = *reinterpret_cast<uint4*>(ku.s);
+      else
+        kf_last = ku.v;
+      *reinterpret_cast<uint4*>(vimg + dblk * FRAG) = *reinterpret_cast<uint4*>(vu.s);
+    }
+  }
+
+  float dk_acc[DCOL][16], dv_acc[DCOL][16];
+#pragma unroll
+  for (int dc = 0; dc < DCOL; ++dc)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dk_acc[dc][r] = dv_acc[dc][r] = 0.f;
+
+  int q_lo, q_hi;
+  // document mask (all as in the split kernels): causal q_lo, the block's last
+  // k row has the largest end; this lane's end and the wave's smallest /
+  // largest one for the mask-free test and the per-wave dead-tile skip
+  [[maybe_unused]] int dend = 0, dend_wmin = 0, dend_wmax = 0, kv0u = kv0w;
+  if constexpr (MOD == MOD_DOCUMENT) {
+    const int kvb0 = kvtile * KPB;
+    const int* de = doc_end + (long)b * Skv;
+    q_lo = kvb0 & ~31;
+    q_hi = max(q_lo, doc_clamp(de[min(kvb0 + KPB - 1, Skv - 1)], Sq));
+    kv0u = __builtin_amdgcn_readfirstlane(kv0w);
+    dend = de[k_valid ? krow : 0];
+    dend_wmin = de[min(kv0u, Skv - 1)];
+    dend_wmax = de[min(kv0u + 31, Skv - 1)];
+  } else {
+    q_range_for_kv<MOD>(kvtile * KPB, KPB, q_off, Sq, modarg, q_lo, q_hi);
+  }
+
+  // T14 staging of one 32-row q tile: threads 0..255 own Q chunks (2 rows x
+  // 8 d), threads 256..511 own dO chunks; lanes 0-31 of wave 0 carry the
+  // tile's lse / Drow through the same load -> write pipeline.
+  constexpr int CH_TOT = (32 / 2) * (D / 8);  // 256 chunks per tensor-tile
+  static_assert(2 * CH_TOT == TPB, "one chunk pair per thread");
+  uint4 sreg[2];
+  float st_l = 0.f, st_d = 0.f;
+  // waves 0-3 stage Q, waves 4-7 dO: wave-uniform, so the source pointer and
+  // row stride stay in SGPRs
+  const bool isq = __builtin_amdgcn_readfirstlane(wave) < NW / 2;
+  const int su = isq ? tid : tid - CH_TOT;
+  const int srow = (su / (D / 8)) * 2;
+  const int sd0 = (su % (D / 8)) * 8;
+
+  auto stage_load = [&](int hq_, int q0) {
+    if (tid < 32) {
+      const int qr = q0 + tid;
+      st_l = (qr < Sq) ? lse[((long)b * Hq + hq_) * Sq + qr] : INFINITY;
+      st_d = (qr < Sq) ? drow[((long)b * Sq + qr) * Hq + hq_] : 0.f;
+    }
+    const __hip_bfloat16* src = isq ? q : dout;
+    const long rs_ = isq ? q_rs : do_rs;
+    const bool ok0 = q0 + srow < Sq;
+    const bool ok1 = q0 + srow + 1 < Sq;
+    const long base = ((long)b * Sq + q0 + srow) * rs_ + (long)hq_ * D + sd0;
+    sreg[0] = ok0 ? *reinterpret_cast<const uint4*>(src + base) : uint4{0, 0, 0, 0};
+    sreg[1] = ok1 ? *reinterpret_cast<const uint4*>(src + base + rs_) : uint4{0, 0, 0, 0};
+  };
+  auto stage_write = [&](int bufsel) {
+    __hip_bfloat16* dst = smem + bufsel * TILE + (isq ? 0 : 32 * D);
+    *reinterpret_cast<uint4*>(dst + rm_swz<D>(srow, sd0)) = sreg[0];
+    *reinterpret_cast<uint4*>(dst + rm_swz<D>(srow + 1, sd0)) = sreg[1];
+    if (tid < 32) {
+      stats_lds[bufsel][0][tid] = st_l * LOG2E;
+      stats_lds[bufsel][1][tid] = st_d;
+    }
+  };
+
+  // iterate (GQA head, q tile) pairs with a flat prefetch pipeline
+  const int ntiles = (q_hi - q_lo + 31) / 32;
+  const int total_iters = group * ntiles;
+  if (total_iters == 0) goto store;
+
+  {
+    auto iter_to = [&](int it, int& hq_, int& q0) {
+      hq_ = hkv * group + it / ntiles;
+      q0 = q_lo + (it % ntiles) * 32;
+    };
+    int hq0_, q00;
+    iter_to(0, hq0_, q00);
+    stage_load(hq0_, q00);
+    stage_write(0);
+    __syncthreads();
+
+    // this wave's compute for one (GQA head, q tile) staged in buffer buf
+    auto tile_compute = [&](int hq_, int q0, int buf) {
+      const float slope2 = (MOD == MOD_ALIBI) ? slopes[hq_] * LOG2E : 0.f;
+      const __hip_bfloat16* q_lds = smem + buf * TILE;
+      const __hip_bfloat16* do_lds = q_lds + 32 * D;
+
+      // S = mfma(Q, K^T), dP = mfma(dO, V^T): A = Q / dO rm frags, B = K / V
+      // frags from the wave's image; element (r=q_local, c=k_local)
+      f32x16 s_acc = {}, dp_acc = {};
+      // opaque copies of the lane id (here and before the accumulates): the
+      // swizzled LDS offsets derived from them are re-formed per iteration
+      // (a few VALU ops) instead of being hoisted out of the loop into ~16
+      // registers that would be live across the P / dS phase, where the
+      // kernel sits on the 256-VGPR limit
+      int lane_s = lane;
+      asm volatile("" : "+v"(lane_s));
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dblk = 0; dblk < DBLK; ++dblk) {
+        const int off = rm_swz<D>(lane_s & 31, dblk * 16 + (lane_s >> 5) * 8);
+        Bf16x8U qa, da, kb, vb;
+        *reinterpret_cast<uint4*>(qa.s) = *reinterpret_cast<const uint4*>(q_lds + off);
+        if (dblk < DBLK - 1)
+          *reinterpret_cast<uint4*>(kb.s) = *reinterpret_cast<const uint4*>(kimg + dblk * FRAG);
+        else
+          kb.v = kf_last;
+        *reinterpret_cast<uint4*>(da.s) = *reinterpret_cast<const uint4*>(do_lds + off);
+        *reinterpret_cast<uint4*>(vb.s) = *reinterpret_cast<const uint4*>(vimg + dblk * FRAG);
+        s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa.v, kb.v, s_acc, 0, 0, 0);
+        dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da.v, vb.v, dp_acc, 0, 0, 0);
+      }
+      __builtin_amdgcn_s_setprio(0);
+
+      // interior (q tile entirely below this wave's k rows): mask-free
+      bool full = q0 + 31 < Sq;
+      if constexpr (MOD == MOD_CAUSAL) {
+        full = full && (q0 + q_off >= kv0w + 31);
+      } else if constexpr (MOD == MOD_SLIDING_WINDOW) {
+        full = full && (q0 + q_off >= kv0w + 31) &&
+               ((q0 + 31 + q_off) - kv0w < modarg);
+      } else if constexpr (MOD == MOD_PREFIX_LM) {
+        full = full && ((q0 + q_off >= kv0w + 31) || (kv0w + 31 < modarg));
+      } else if constexpr (MOD == MOD_DOCUMENT) {
+        // the wave's first k row has its smallest end
+        full = full && (q0 >= kv0u + 31) && (q0 + 31 < dend_wmin);
+      } else {
+        full = false;  // MOD_NONE boundary Sq checks + ALIBI slope
+      }
+
+      float pv[16], dsv[16];
+      bwd_p_ds_tile<MOD, true, true>(
+          s_acc, dp_acc, &stats_lds[buf][0][0], &stats_lds[buf][1][0], full, hi, q0, q_off,
+          krow, k_valid, Sq, Skv, modarg, scale, scale2, slope2, dend, nullptr, nullptr, 0, 0,
+          pv, dsv);
+
+      // dV += P^T . dO first: the packed P fragments die before dK starts
+      int lane_t = lane;
+      {
+        bf16x8 a0, a1;
+        acc_to_afrag(pv, a0, a1);
+        asm volatile("" : "+v"(lane_t));
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int dc = 0; dc < DCOL; ++dc) {
+          f32x16 acc;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[r] = dv_acc[dc][r];
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+            bf16x8 xb = tr16_frag<D>(do_lds, ks * 16 + (lane_t >> 5) * 8, dc * 32, lane_t);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks == 0 ? a0 : a1, xb, acc, 0, 0, 0);
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dv_acc[dc][r] = acc[r];
+        }
+        __builtin_amdgcn_s_setprio(0);
+      }
+      // dK += dS^T . Q
+      {
+        bf16x8 a0, a1;
+        acc_to_afrag(dsv, a0, a1);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int dc = 0; dc < DCOL; ++dc) {
+          f32x16 acc;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[r] = dk_acc[dc][r];
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+            bf16x8 xb = tr16_frag<D>(q_lds, ks * 16 + (lane_t >> 5) * 8, dc * 32, lane_t);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks == 0 ? a0 : a1, xb, acc, 0, 0, 0);
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dk_acc[dc][r] = acc[r];
+        }
+        __builtin_amdgcn_s_setprio(0);
+      }
+    };
+
+    int buf = 0;
+    for (int it = 0; it < total_iters; ++it) {
+      const bool has_next = it + 1 < total_iters;
+      // the next tile loads during this tile's compute and is written to
+      // buf^1 after it (buf^1 was last read before the previous barrier)
+      if (has_next) {
+        int nhq, nq0;
+        iter_to(it + 1, nhq, nq0);
+        stage_load(nhq, nq0);
+      }
+      int hq_, q0;
+      iter_to(it, hq_, q0);
+      // document: a q tile wholly above the wave's first k row, or wholly
+      // past its last k row's document, is dead for the whole wave — skip
+      // the compute only (all operands are SGPRs), staging and barrier run
+      bool live = true;
+      if constexpr (MOD == MOD_DOCUMENT)
+        live = kv0u < Skv && q0 + 31 >= kv0u && q0 < dend_wmax;
+      if (live) tile_compute(hq_, q0, buf);
+
+      if (has_next) stage_write(buf ^ 1);
+      __syncthreads();
+      buf ^= 1;
+    }
+  }
+
+store:
+  // store: element (r=k_local, c=d_local)
+  {
+    const int dl = lane & 31;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int r = acc_row(reg, hi);
+      const int k_r = kv0w + r;
+      if (k_r >= Skv) continue;
+      const long o = (long)hkv * D + dl;
+      __hip_bfloat16* outk = dk_out + ((long)b * Skv + k_r) * dk_rs + o;
+      __hip_bfloat16* outv = dv_out + ((long)b * Skv + k_r) * dv_rs + o;
+#pragma unroll
+      for (int dc = 0; dc < DCOL; ++dc) {
+        outk[dc * 32] = __float2bfloat16(dk_acc[dc][reg]);
+        outv[dc * 32] = __float2bfloat16(dv_acc[dc][reg]);
+      }
+    }
+  }
+}
+
 template <int D, int MOD, int NW>
 void launch_bwd_all(dim3 gq, dim3 gkv, dim3 block, hipStream_t stream,
                     const __hip_bfloat16* q, const __hip_bfloat16* k, const __hip_bfloat16* v,
@@ -817,9 +1154,19 @@ void launch_bwd_all(dim3 gq, dim3 gkv, dim3 block, hipStream_t stream,
                     __hip_bfloat16* dq, __hip_bfloat16* dk, __hip_bfloat16* dv,
                     const float* slopes, int B, int Sq, int Skv, int Hq, int Hkv,
                     float scale, int modarg, long q_rs, long k_rs, long v_rs, long do_rs,
-                    long dq_rs, long dk_rs, long dv_rs) {
+                    long dq_rs, long dk_rs, long dv_rs, bool split) {
   attn_bwd_dq_kernel<D, MOD, NW><<<gq, block, 0, stream>>>(
       q, k, v, dout, lse, drow, dq, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs);
+  // merged dK+dV: D=128 at 8 waves/block (D=64 and the other block sizes
+  // keep the split pair)
+  if constexpr (D == 128 && NW == 8) {
+    if (!split) {
+      attn_bwd_dkdv_kernel<D, MOD><<<gkv, block, 0, stream>>>(
+          q, k, v, dout, lse, drow, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg,
+          q_rs, k_rs, v_rs, do_rs, dk_rs, dv_rs);
+      return;
+    }
+  }
   attn_bwd_dkv_kernel<D, MOD, true, NW><<<gkv, block, 0, stream>>>(
       q, k, v, dout, lse, drow, dk, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dk_rs);
   attn_bwd_dkv_kernel<D, MOD, false, NW><<<gkv, block, 0, stream>>>(
@@ -833,19 +1180,19 @@ void launch_all_nw(dim3 gq, dim3 gkv, dim3 block, hipStream_t stream,
                    __hip_bfloat16* dq, __hip_bfloat16* dk, __hip_bfloat16* dv,
                    const float* slopes, int B, int Sq, int Skv, int Hq, int Hkv,
                    float scale, int modarg, long q_rs, long k_rs, long v_rs, long do_rs,
-                   long dq_rs, long dk_rs, long dv_rs) {
+                   long dq_rs, long dk_rs, long dv_rs, bool split) {
   if (bwd_nw() == 16)
     launch_bwd_all<D, MOD, 16>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv,
                                slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs,
-                               do_rs, dq_rs, dk_rs, dv_rs);
+                               do_rs, dq_rs, dk_rs, dv_rs, split);
   else if (bwd_nw() == 4)
     launch_bwd_all<D, MOD, 4>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv,
                               slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs,
-                              do_rs, dq_rs, dk_rs, dv_rs);
+                              do_rs, dq_rs, dk_rs, dv_rs, split);
   else
     launch_bwd_all<D, MOD, 8>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv,
                               slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs,
-                              do_rs, dq_rs, dk_rs, dv_rs);
+                              do_rs, dq_rs, dk_rs, dv_rs, split);
 }
 
 template <int D>
@@ -855,34 +1202,32 @@ void launch_bwd_mod(int mod, dim3 gq, dim3 gkv, dim3 block, hipStream_t stream,
                     __hip_bfloat16* dq, __hip_bfloat16* dk, __hip_bfloat16* dv,
                     const float* slopes, int B, int Sq, int Skv, int Hq, int Hkv,
                     float scale, int modarg, long q_rs, long k_rs, long v_rs, long do_rs,
-                    long dq_rs, long dk_rs, long dv_rs) {
+                    long dq_rs, long dk_rs, long dv_rs, bool split) {
   switch (mod) {
     case MOD_NONE:
-      launch_all_nw<D, MOD_NONE>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs);
+      launch_all_nw<D, MOD_NONE>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
       break;
     case MOD_CAUSAL:
-      launch_all_nw<D, MOD_CAUSAL>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs);
+      launch_all_nw<D, MOD_CAUSAL>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
       break;
     case MOD_SLIDING_WINDOW:
-      launch_all_nw<D, MOD_SLIDING_WINDOW>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs);
+      launch_all_nw<D, MOD_SLIDING_WINDOW>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
       break;
     case MOD_PREFIX_LM:
-      launch_all_nw<D, MOD_PREFIX_LM>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs);
+      launch_all_nw<D, MOD_PREFIX_LM>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
       break;
     case MOD_ALIBI:
-      launch_all_nw<D, MOD_ALIBI>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs);
+      launch_all_nw<D, MOD_ALIBI>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
       break;
     default:
       TORCH_CHECK(false, "attn_bwd: unknown mod ", mod);
   }
 }
 
-}  // namespace
-
-std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
-                                     at::Tensor dout, at::Tensor lse, double scale, long mod,
-                                     long modarg, at::Tensor slopes,
-                                     at::Tensor dq, at::Tensor dk, at::Tensor dv) {
+std::vector<at::Tensor> attn_bwd_impl(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                      at::Tensor dout, at::Tensor lse, double scale, long mod,
+                                      long modarg, at::Tensor slopes,
+                                      at::Tensor dq, at::Tensor dk, at::Tensor dv, bool split) {
   TORCH_CHECK(q.is_cuda());
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "attn_bwd: bf16 only");
   auto rs = [](at::Tensor& t) {
@@ -941,13 +1286,33 @@ std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, a
     launch_bwd_mod<64>((int)mod, gq, gkv, block, stream, qp, kp, vp, dop,
                        lse.data_ptr<float>(), drow.data_ptr<float>(), dqp, dkp, dvp, sl,
                        B, Sq, Skv, Hq, Hkv, (float)scale, (int)modarg, q_rs, k_rs, v_rs, do_rs,
-                       dq_rs, dk_rs, dv_rs);
+                       dq_rs, dk_rs, dv_rs, split);
   else
     launch_bwd_mod<128>((int)mod, gq, gkv, block, stream, qp, kp, vp, dop,
                         lse.data_ptr<float>(), drow.data_ptr<float>(), dqp, dkp, dvp, sl,
                         B, Sq, Skv, Hq, Hkv, (float)scale, (int)modarg, q_rs, k_rs, v_rs, do_rs,
-                        dq_rs, dk_rs, dv_rs);
+                        dq_rs, dk_rs, dv_rs, split);
   return {dq, dk, dv};
+}
+
+}  // namespace
+
+std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                     at::Tensor dout, at::Tensor lse, double scale, long mod,
+                                     long modarg, at::Tensor slopes,
+                                     at::Tensor dq, at::Tensor dk, at::Tensor dv) {
+  return attn_bwd_impl(q, k, v, o, dout, lse, scale, mod, modarg, slopes, dq, dk, dv,
+                       bwd_split());
+}
+
+// attn_bwd on the split dK / dV kernels whatever the default is, so a test
+// can compare the two paths inside one process.
+std::vector<at::Tensor> attn_bwd_split(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                       at::Tensor dout, at::Tensor lse, double scale, long mod,
+                                       long modarg, at::Tensor slopes) {
+  auto none = at::empty({0}, q.options());
+  return attn_bwd_impl(q, k, v, o, dout, lse, scale, mod, modarg, slopes,
+                       none, none.clone(), none.clone(), true);
 }
 
 // Backward of attn_fwd_blockmask (trainable flex attention): same device mask
@@ -1130,6 +1495,16 @@ std::vector<at::Tensor> attn_bwd_doc_out(at::Tensor q, at::Tensor k, at::Tensor 
         qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()), nullptr,
         B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dq_rs,
         nullptr, nullptr, nullptr, nullptr, dsp);
+    // merged dK+dV at D=128, as in attn_bwd_out
+    if constexpr (DD == 128) {
+      if (!bwd_split()) {
+        attn_bwd_dkdv_kernel<DD, MOD_DOCUMENT><<<gkv, block, 0, stream>>>(
+            qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
+            reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()), nullptr,
+            B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dk_rs, dv_rs, dep);
+        return;
+      }
+    }
     attn_bwd_dkv_kernel<DD, MOD_DOCUMENT, true, 8><<<gkv, block, 0, stream>>>(
         qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()), nullptr,
         B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dk_rs,

@@ -48,6 +48,9 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, doubl
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                  at::Tensor dout, at::Tensor lse, double scale, long mod,
                                  long modarg, at::Tensor slopes);
+std::vector<at::Tensor> attn_bwd_split(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                       at::Tensor dout, at::Tensor lse, double scale, long mod,
+                                       long modarg, at::Tensor slopes);
 std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                      at::Tensor dout, at::Tensor lse, double scale, long mod,
                                      long modarg, at::Tensor slopes,
@@ -122,6 +125,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd_blockmask", &attn_fwd_blockmask,
         "flash attention fwd with device block-mask/bits/bias (K2 flex)");
   m.def("attn_bwd", &attn_bwd, "flash attention backward (dq, dk, dv)");
+  m.def("attn_bwd_split", &attn_bwd_split,
+        "attn_bwd on the split dK / dV kernels (reference for the merged dK+dV kernel)");
   m.def("attn_bwd_out", &attn_bwd_out,
         "flash attention backward into strided out views (fused dQKV)");
   m.def("attn_bwd_blockmask", &attn_bwd_blockmask,
