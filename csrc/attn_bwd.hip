@@ -14,12 +14,14 @@
 //                 kernel replaced — each streams the same Q and dO tiles and
 //                 recomputes the same S and P. Still the path for D=64 (both
 //                 fit registers there at 2-3 waves/SIMD, not ported), for
-//                 NW != 8, for the blockmask entry point (not ported: its
-//                 bits / bias addressing wants registers the merged kernel
-//                 does not have to spare without a re-tune) and under
+//                 the blockmask entry point (not ported: its bits / bias
+//                 addressing wants registers the merged kernel does not have
+//                 to spare without a re-tune) and under
 //                 MCDP_ATTN_BWD_SPLIT=1; attn_bwd_split always runs
 //                 it. Both paths share bwd_p_ds_tile, and their dK and dV
 //                 are bit-identical (tests/test_gpu_attn_bwd_merged.py).
+//   Every entry point goes through run_bwd (bottom of the file): preprocess,
+//   dQ, then the merged kernel or the split pair — one launch site per kernel.
 //
 // Same gfx950 structure as the forward (attn_fwd.hip): 8 waves/block sharing
 // every staged tile, DOUBLE-BUFFERED tiles with one barrier per iteration,
@@ -35,7 +37,7 @@
 // LDS copies are staged anywhere in the backward.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "attn_common.h"
+#include "attn_launch.h"
 
 namespace {
 
@@ -45,21 +47,8 @@ namespace {
 constexpr int KVB_FILE = 64;
 constexpr float LOG2E = 1.4426950408889634f;
 
-// waves per block (8 or 16): 16-wave blocks halve staging traffic and
-// barrier frequency per unit of MFMA work at the same 4 waves/SIMD
-// (1 block/CU instead of 2). Env MCDP_ATTN_BWD_NW selects at launch.
-inline int bwd_nw() {
-  static int nw = []() {
-    const char* e = getenv("MCDP_ATTN_BWD_NW");
-    // NW=4 measured 2.4x SLOWER at D=128 (call7: 139 vs 331 TF) once the
-    // launch bug that faked its earlier win was fixed — default stays 8.
-    return e ? atoi(e) : 8;
-  }();
-  return nw;
-}
-
 // MCDP_ATTN_BWD_SPLIT=1: run the split dK and dV kernels where the merged
-// dK+dV kernel is the default (D=128, 8 waves/block).
+// dK+dV kernel is the default (D=128, every mod but blockmask).
 inline bool bwd_split() {
   static bool split = []() {
     const char* e = getenv("MCDP_ATTN_BWD_SPLIT");
@@ -112,9 +101,27 @@ __device__ __forceinline__ void q_range_for_kv(int kv0, int kpb, int q_off, int 
   }
 }
 
+// MOD_DOCUMENT set-up of a kv-tile block: causal q_lo, and the block's last k
+// row has the largest end (an ill-formed end in front of q_lo leaves an empty
+// range: straight to store). Then this lane's end and the wave's smallest /
+// largest one (its first / last k row's; wave-uniform loads) for the
+// mask-free test and the per-wave dead-tile skip.
+__device__ __forceinline__ void doc_range_for_kv(
+    const int* __restrict__ doc_end, int b, int Sq, int Skv, int kvb0, int kpb, int kv0w,
+    int krow, bool k_valid, int& q_lo, int& q_hi, int& dend, int& dend_wmin, int& dend_wmax,
+    int& kv0u) {
+  const int* de = doc_end + (long)b * Skv;
+  q_lo = kvb0 & ~31;
+  q_hi = max(q_lo, doc_clamp(de[min(kvb0 + kpb - 1, Skv - 1)], Sq));
+  kv0u = __builtin_amdgcn_readfirstlane(kv0w);  // the wave's first k row, in an SGPR
+  dend = de[k_valid ? krow : 0];
+  dend_wmin = de[min(kv0u, Skv - 1)];
+  dend_wmax = de[min(kv0u + 31, Skv - 1)];
+}
+
 // ---------------- dQ kernel (block per q-tile of QPB rows) ----------------
-template <int D, int MOD, int NW>
-__global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
+template <int D, int MOD>
+__global__ __launch_bounds__(8 * WAVE) void attn_bwd_dq_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ drow,
@@ -132,9 +139,9 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dq_kernel(
     const __hip_bfloat16* __restrict__ bias = nullptr,
     // MOD_DOCUMENT only: doc_start int32 [B,Sq] (see attn_fwd.hip)
     const int* __restrict__ doc_start = nullptr) {
-  // the mask tensors are laid out for the forward's 256-row q blocks
-  static_assert(MOD != MOD_BLOCKMASK || NW == 8, "blockmask bwd is NW=8 only");
-  static_assert(MOD != MOD_DOCUMENT || NW == 8, "document bwd is built for NW=8 only");
+  // waves per block (NW=4 measured 2.4x slower at D=128: 139 vs 331 TF); the
+  // blockmask tensors are laid out for the resulting 256-row q blocks
+  constexpr int NW = 8;
   constexpr int TPB = NW * WAVE;
   constexpr int QPB = 32 * NW;
   constexpr int DBLK = D / 16;
@@ -502,11 +509,11 @@ __device__ __forceinline__ void bwd_p_ds_tile(
 }
 
 // ---------------- dK / dV kernels (block per kv-tile, loop GQA group) -------
-// The split pair: the path for D=64, NW != 8, the blockmask entry point and
+// The split pair: the path for D=64, the blockmask entry point and
 // MCDP_ATTN_BWD_SPLIT=1; everything else runs the merged kernel below.
 // WANT_DK: true -> dK (needs dP: V frags + dO rm); false -> dV (needs dO^T).
-template <int D, int MOD, bool WANT_DK, int NW>
-__global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
+template <int D, int MOD, bool WANT_DK>
+__global__ __launch_bounds__(8 * WAVE) void attn_bwd_dkv_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ drow,
@@ -523,8 +530,7 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
     // MOD_DOCUMENT only: doc_end int32 [B,Skv], one past the last position of
     // each row's document (non-decreasing along s; same for every head)
     const int* __restrict__ doc_end = nullptr) {
-  static_assert(MOD != MOD_BLOCKMASK || NW == 8, "blockmask bwd is NW=8 only");
-  static_assert(MOD != MOD_DOCUMENT || NW == 8, "document bwd is built for NW=8 only");
+  constexpr int NW = 8;  // waves per block (NW=4 measured 2.4x slower at D=128)
   constexpr int TPB = NW * WAVE;
   constexpr int KPB = 32 * NW;
   constexpr int DBLK = D / 16;
@@ -577,6 +583,9 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
     for (int r = 0; r < 16; ++r) acc_out[dc][r] = 0.f;
 
   int q_lo, q_hi;
+  // document mask: this lane's doc end, the wave's smallest / largest one and
+  // its first k row in an SGPR (doc_range_for_kv)
+  [[maybe_unused]] int dend = 0, dend_wmin = 0, dend_wmax = 0, kv0u = kv0w;
   if constexpr (MOD == MOD_BLOCKMASK) {
     // union of the live q-tile ranges over this kv head's GQA group, so the
     // flat (head, q tile) iteration below stays uniform; heads with nothing
@@ -593,11 +602,8 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
     q_lo = (t_hi > 0) ? t_lo * 32 : 0;
     q_hi = (t_hi > 0) ? min(Sq, t_hi * 32) : 0;  // empty: straight to store
   } else if constexpr (MOD == MOD_DOCUMENT) {
-    // causal q_lo; the block's last k row has the largest end. An ill-formed
-    // end in front of q_lo leaves an empty range (straight to store).
-    const int kvb0 = kvtile * KPB;
-    q_lo = kvb0 & ~31;
-    q_hi = max(q_lo, doc_clamp(doc_end[(long)b * Skv + min(kvb0 + KPB - 1, Skv - 1)], Sq));
+    doc_range_for_kv(doc_end, b, Sq, Skv, kvtile * KPB, KPB, kv0w, krow, k_valid, q_lo, q_hi,
+                     dend, dend_wmin, dend_wmax, kv0u);
   } else {
     q_range_for_kv<MOD>(kvtile * KPB, KPB, q_off, Sq, modarg, q_lo, q_hi);
   }
@@ -606,17 +612,6 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
   [[maybe_unused]] const int nq32 = (Sq + 31) / 32;
   [[maybe_unused]] const int nkvt = (Skv + 63) / 64;
   [[maybe_unused]] const int kvb8 = (Skv + 7) / 8;
-  // document mask: this lane's upper bound, and the wave's smallest / largest
-  // one (its first / last k row's; wave-uniform loads) for the mask-free test
-  // and the per-wave dead-tile skip
-  [[maybe_unused]] int dend = 0, dend_wmin = 0, dend_wmax = 0, kv0u = kv0w;
-  if constexpr (MOD == MOD_DOCUMENT) {
-    const int* de = doc_end + (long)b * Skv;
-    kv0u = __builtin_amdgcn_readfirstlane(kv0w);  // the wave's first k row, in an SGPR
-    dend = de[k_valid ? krow : 0];
-    dend_wmin = de[min(kv0u, Skv - 1)];
-    dend_wmax = de[min(kv0u + 31, Skv - 1)];
-  }
 
   // sub-tiles per barrier: dV runs two (32 MFMAs/barrier, 220-238 VGPR);
   // dK holds V fragments too and spills at NP=2, so it stays at one.
@@ -628,8 +623,9 @@ __global__ __launch_bounds__(NW* WAVE) void attn_bwd_dkv_kernel(
   // (2 rows x 8 d), threads 256..511 own dO chunks; each thread carries one
   // chunk pair per sub-tile.
   constexpr int CH_TOT = (32 / 2) * (D / 8);  // 256 chunks per tensor-tile
-  // chunk units per thread: 1 at NW=8 (Q half / dO half split across the
-  // 512 threads), 2 at NW=4 — each unit decides Q-vs-dO by its global index
+  // chunk units per thread: 1 (Q half / dO half split across the 512
+  // threads; D=64 leaves the upper 256 idle) — each unit decides Q-vs-dO by
+  // its global index
   constexpr int NU = (2 * CH_TOT + TPB - 1) / TPB;
   uint4 sreg[NU][2];  // ONE sub-tile's chunk pairs at a time (split-half
                       // staging: load s -> compute s-1 -> write s)
@@ -930,19 +926,11 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dkdv_kernel(
     for (int r = 0; r < 16; ++r) dk_acc[dc][r] = dv_acc[dc][r] = 0.f;
 
   int q_lo, q_hi;
-  // document mask (all as in the split kernels): causal q_lo, the block's last
-  // k row has the largest end; this lane's end and the wave's smallest /
-  // largest one for the mask-free test and the per-wave dead-tile skip
+  // document mask, as in the split kernels (doc_range_for_kv)
   [[maybe_unused]] int dend = 0, dend_wmin = 0, dend_wmax = 0, kv0u = kv0w;
   if constexpr (MOD == MOD_DOCUMENT) {
-    const int kvb0 = kvtile * KPB;
-    const int* de = doc_end + (long)b * Skv;
-    q_lo = kvb0 & ~31;
-    q_hi = max(q_lo, doc_clamp(de[min(kvb0 + KPB - 1, Skv - 1)], Sq));
-    kv0u = __builtin_amdgcn_readfirstlane(kv0w);
-    dend = de[k_valid ? krow : 0];
-    dend_wmin = de[min(kv0u, Skv - 1)];
-    dend_wmax = de[min(kv0u + 31, Skv - 1)];
+    doc_range_for_kv(doc_end, b, Sq, Skv, kvtile * KPB, KPB, kv0w, krow, k_valid, q_lo, q_hi,
+                     dend, dend_wmin, dend_wmax, kv0u);
   } else {
     q_range_for_kv<MOD>(kvtile * KPB, KPB, q_off, Sq, modarg, q_lo, q_hi);
   }
@@ -1147,151 +1135,73 @@ store:
   }
 }
 
-template <int D, int MOD, int NW>
-void launch_bwd_all(dim3 gq, dim3 gkv, dim3 block, hipStream_t stream,
-                    const __hip_bfloat16* q, const __hip_bfloat16* k, const __hip_bfloat16* v,
-                    const __hip_bfloat16* dout, const float* lse, const float* drow,
-                    __hip_bfloat16* dq, __hip_bfloat16* dk, __hip_bfloat16* dv,
-                    const float* slopes, int B, int Sq, int Skv, int Hq, int Hkv,
-                    float scale, int modarg, long q_rs, long k_rs, long v_rs, long do_rs,
-                    long dq_rs, long dk_rs, long dv_rs, bool split) {
-  attn_bwd_dq_kernel<D, MOD, NW><<<gq, block, 0, stream>>>(
-      q, k, v, dout, lse, drow, dq, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs);
-  // merged dK+dV: D=128 at 8 waves/block (D=64 and the other block sizes
-  // keep the split pair)
-  if constexpr (D == 128 && NW == 8) {
-    if (!split) {
-      attn_bwd_dkdv_kernel<D, MOD><<<gkv, block, 0, stream>>>(
-          q, k, v, dout, lse, drow, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg,
-          q_rs, k_rs, v_rs, do_rs, dk_rs, dv_rs);
-      return;
-    }
-  }
-  attn_bwd_dkv_kernel<D, MOD, true, NW><<<gkv, block, 0, stream>>>(
-      q, k, v, dout, lse, drow, dk, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dk_rs);
-  attn_bwd_dkv_kernel<D, MOD, false, NW><<<gkv, block, 0, stream>>>(
-      q, k, v, dout, lse, drow, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dv_rs);
-}
-
-template <int D, int MOD>
-void launch_all_nw(dim3 gq, dim3 gkv, dim3 block, hipStream_t stream,
-                   const __hip_bfloat16* q, const __hip_bfloat16* k, const __hip_bfloat16* v,
-                   const __hip_bfloat16* dout, const float* lse, const float* drow,
-                   __hip_bfloat16* dq, __hip_bfloat16* dk, __hip_bfloat16* dv,
-                   const float* slopes, int B, int Sq, int Skv, int Hq, int Hkv,
-                   float scale, int modarg, long q_rs, long k_rs, long v_rs, long do_rs,
-                   long dq_rs, long dk_rs, long dv_rs, bool split) {
-  if (bwd_nw() == 16)
-    launch_bwd_all<D, MOD, 16>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv,
-                               slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs,
-                               do_rs, dq_rs, dk_rs, dv_rs, split);
-  else if (bwd_nw() == 4)
-    launch_bwd_all<D, MOD, 4>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv,
-                              slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs,
-                              do_rs, dq_rs, dk_rs, dv_rs, split);
-  else
-    launch_bwd_all<D, MOD, 8>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv,
-                              slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs,
-                              do_rs, dq_rs, dk_rs, dv_rs, split);
-}
-
-template <int D>
-void launch_bwd_mod(int mod, dim3 gq, dim3 gkv, dim3 block, hipStream_t stream,
-                    const __hip_bfloat16* q, const __hip_bfloat16* k, const __hip_bfloat16* v,
-                    const __hip_bfloat16* dout, const float* lse, const float* drow,
-                    __hip_bfloat16* dq, __hip_bfloat16* dk, __hip_bfloat16* dv,
-                    const float* slopes, int B, int Sq, int Skv, int Hq, int Hkv,
-                    float scale, int modarg, long q_rs, long k_rs, long v_rs, long do_rs,
-                    long dq_rs, long dk_rs, long dv_rs, bool split) {
-  switch (mod) {
-    case MOD_NONE:
-      launch_all_nw<D, MOD_NONE>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
-      break;
-    case MOD_CAUSAL:
-      launch_all_nw<D, MOD_CAUSAL>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
-      break;
-    case MOD_SLIDING_WINDOW:
-      launch_all_nw<D, MOD_SLIDING_WINDOW>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
-      break;
-    case MOD_PREFIX_LM:
-      launch_all_nw<D, MOD_PREFIX_LM>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
-      break;
-    case MOD_ALIBI:
-      launch_all_nw<D, MOD_ALIBI>(gq, gkv, block, stream, q, k, v, dout, lse, drow, dq, dk, dv, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs, do_rs, dq_rs, dk_rs, dv_rs, split);
-      break;
-    default:
-      TORCH_CHECK(false, "attn_bwd: unknown mod ", mod);
-  }
-}
-
-std::vector<at::Tensor> attn_bwd_impl(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
-                                      at::Tensor dout, at::Tensor lse, double scale, long mod,
-                                      long modarg, at::Tensor slopes,
-                                      at::Tensor dq, at::Tensor dk, at::Tensor dv, bool split) {
-  TORCH_CHECK(q.is_cuda());
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "attn_bwd: bf16 only");
-  auto rs = [](at::Tensor& t) {
-    const int S = t.size(1), H = t.size(2), D = t.size(3);
-    if (!(t.stride(3) == 1 && t.stride(2) == D && t.stride(0) == (long)S * t.stride(1)))
-      t = t.contiguous();
-    return t.stride(1);
-  };
-  const long q_rs = rs(q), k_rs = rs(k), v_rs = rs(v), do_rs = rs(dout);
-  o = o.contiguous();
-  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Skv = k.size(1), Hkv = k.size(2);
-  TORCH_CHECK(D == 64 || D == 128, "attn_bwd: head_dim must be 64 or 128");
-  // outputs may be pre-allocated row-strided views (slices of a fused dQKV
-  // grad buffer) — element (b,s,h,d) at (b*S+s)*stride(1) + h*D + d
-  auto check_out = [&](at::Tensor& t, int S_, int H_) {
-    if (t.numel() == 0) {
-      t = at::empty({B, S_, H_, D}, q.options());
-    } else {
-      TORCH_CHECK(t.size(0) == B && t.size(1) == S_ && t.size(2) == H_ && t.size(3) == D &&
-                      t.stride(3) == 1 && t.stride(2) == D &&
-                      t.stride(0) == (long)S_ * t.stride(1),
-                  "attn_bwd: bad out view");
-    }
-    return t.stride(1);
-  };
-  const long dq_rs = check_out(dq, Sq, Hq);
-  const long dk_rs = check_out(dk, Skv, Hkv);
-  const long dv_rs = check_out(dv, Skv, Hkv);
-  auto drow = at::empty({(long)B * Sq * Hq}, q.options().dtype(at::kFloat));
+// The one backward launch sequence: Drow, dQ, then dK and dV. 8 waves per
+// block of 256 q rows (dQ) / 256 kv rows (dK, dV).
+template <int MOD>
+void run_bwd(const AttnArgs& a, const at::Tensor& q, bool force_split) {
+  auto drow_t = at::empty({(long)a.B * a.Sq * a.Hq}, q.options().dtype(at::kFloat));
+  const float* drow = drow_t.data_ptr<float>();
   auto stream = at::cuda::getCurrentHIPStream();
-
   {  // preprocess: 4 rows per wave at D=128 (vectorized 16 B loads)
-    const long rows = (long)B * Sq * Hq;
-    const int rpw = WAVE / (D / 8);
+    const long rows = (long)a.B * a.Sq * a.Hq;
+    const int rpw = WAVE / (a.D / 8);
     const long grid = cdiv(rows, (long)(256 / WAVE) * rpw);
-    bwd_preprocess_kernel<<<grid, 256, 0, stream>>>(
-        reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-        reinterpret_cast<const __hip_bfloat16*>(o.data_ptr()),
-        drow.data_ptr<float>(), rows, D, do_rs, Hq);
+    bwd_preprocess_kernel<<<grid, 256, 0, stream>>>(a.dout, a.o, drow_t.data_ptr<float>(), rows,
+                                                    a.D, a.do_rs, a.Hq);
   }
+  constexpr int BLK = 8 * 32;
+  const dim3 gq(cdiv(a.Sq, BLK), a.Hq, a.B), gkv(cdiv(a.Skv, BLK), a.Hkv, a.B), block(8 * WAVE);
+  const bool split = force_split || bwd_split();
+  with_head_dim(a.D, [&](auto dtag) {
+    constexpr int D = decltype(dtag)::value;
+    attn_bwd_dq_kernel<D, MOD><<<gq, block, 0, stream>>>(
+        a.q, a.k, a.v, a.dout, a.lse, drow, a.dq, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv,
+        a.scale, a.modarg, a.q_rs, a.k_rs, a.v_rs, a.do_rs, a.dq_rs,
+        a.gran, a.bits, a.range, a.bias, a.doc_start);
+    // merged dK+dV at D=128 (D=64 and blockmask keep the split pair)
+    if constexpr (D == 128 && MOD != MOD_BLOCKMASK) {
+      if (!split) {
+        attn_bwd_dkdv_kernel<D, MOD><<<gkv, block, 0, stream>>>(
+            a.q, a.k, a.v, a.dout, a.lse, drow, a.dk, a.dv, a.slopes, a.B, a.Sq, a.Skv, a.Hq,
+            a.Hkv, a.scale, a.modarg, a.q_rs, a.k_rs, a.v_rs, a.do_rs, a.dk_rs, a.dv_rs,
+            a.doc_end);
+        return;
+      }
+    }
+    auto dkv = [&](auto want_dk, __hip_bfloat16* out, long out_rs) {
+      attn_bwd_dkv_kernel<D, MOD, decltype(want_dk)::value><<<gkv, block, 0, stream>>>(
+          a.q, a.k, a.v, a.dout, a.lse, drow, out, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv,
+          a.scale, a.modarg, a.q_rs, a.k_rs, a.v_rs, a.do_rs, out_rs,
+          a.gran, a.bits, a.qrange, a.bias, a.doc_end);
+    };
+    dkv(std::true_type{}, a.dk, a.dk_rs);
+    dkv(std::false_type{}, a.dv, a.dv_rs);
+  });
+}
 
-  const int qpb = 32 * bwd_nw();
-  dim3 gq(cdiv(Sq, qpb), Hq, B);
-  dim3 gkv(cdiv(Skv, qpb), Hkv, B);
-  dim3 block(bwd_nw() * WAVE);
-  const float* sl = slopes.numel() > 0 ? slopes.data_ptr<float>() : nullptr;
-  auto* qp = reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
-  auto* kp = reinterpret_cast<const __hip_bfloat16*>(k.data_ptr());
-  auto* vp = reinterpret_cast<const __hip_bfloat16*>(v.data_ptr());
-  auto* dop = reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr());
-  auto* dqp = reinterpret_cast<__hip_bfloat16*>(dq.data_ptr());
-  auto* dkp = reinterpret_cast<__hip_bfloat16*>(dk.data_ptr());
-  auto* dvp = reinterpret_cast<__hip_bfloat16*>(dv.data_ptr());
-  if (D == 64)
-    launch_bwd_mod<64>((int)mod, gq, gkv, block, stream, qp, kp, vp, dop,
-                       lse.data_ptr<float>(), drow.data_ptr<float>(), dqp, dkp, dvp, sl,
-                       B, Sq, Skv, Hq, Hkv, (float)scale, (int)modarg, q_rs, k_rs, v_rs, do_rs,
-                       dq_rs, dk_rs, dv_rs, split);
-  else
-    launch_bwd_mod<128>((int)mod, gq, gkv, block, stream, qp, kp, vp, dop,
-                        lse.data_ptr<float>(), drow.data_ptr<float>(), dqp, dkp, dvp, sl,
-                        B, Sq, Skv, Hq, Hkv, (float)scale, (int)modarg, q_rs, k_rs, v_rs, do_rs,
-                        dq_rs, dk_rs, dv_rs, split);
+// Checks shared by every entry point. dq/dk/dv may be empty (allocated here)
+// or pre-allocated row-strided views (slices of a fused dQKV grad buffer).
+AttnArgs bwd_args(const char* who, at::Tensor& q, at::Tensor& k, at::Tensor& v, at::Tensor& o,
+                  at::Tensor& dout, at::Tensor& lse, double scale, at::Tensor& dq,
+                  at::Tensor& dk, at::Tensor& dv) {
+  AttnArgs a = check_qkv(who, q, k, v, scale);
+  check_o_dout_lse(who, a, q, o, dout, lse);
+  a.dq_rs = check_out_view(who, dq, q, a.Sq, a.Hq);
+  a.dk_rs = check_out_view(who, dk, q, a.Skv, a.Hkv);
+  a.dv_rs = check_out_view(who, dv, q, a.Skv, a.Hkv);
+  a.dq = bf16_out(dq), a.dk = bf16_out(dk), a.dv = bf16_out(dv);
+  return a;
+}
+
+std::vector<at::Tensor> attn_bwd_impl(const char* who, at::Tensor q, at::Tensor k, at::Tensor v,
+                                      at::Tensor o, at::Tensor dout, at::Tensor lse,
+                                      double scale, long mod, long modarg, at::Tensor slopes,
+                                      at::Tensor dq, at::Tensor dk, at::Tensor dv,
+                                      bool force_split) {
+  AttnArgs a = bwd_args(who, q, k, v, o, dout, lse, scale, dq, dk, dv);
+  check_slopes(who, a, mod, slopes, q);
+  a.modarg = (int)modarg;
+  with_mod(who, mod, [&](auto mtag) { run_bwd<decltype(mtag)::value>(a, q, force_split); });
   return {dq, dk, dv};
 }
 
@@ -1301,8 +1211,15 @@ std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, a
                                      at::Tensor dout, at::Tensor lse, double scale, long mod,
                                      long modarg, at::Tensor slopes,
                                      at::Tensor dq, at::Tensor dk, at::Tensor dv) {
-  return attn_bwd_impl(q, k, v, o, dout, lse, scale, mod, modarg, slopes, dq, dk, dv,
-                       bwd_split());
+  return attn_bwd_impl("attn_bwd_out", q, k, v, o, dout, lse, scale, mod, modarg, slopes,
+                       dq, dk, dv, false);
+}
+
+std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                 at::Tensor dout, at::Tensor lse, double scale, long mod,
+                                 long modarg, at::Tensor slopes) {
+  return attn_bwd_impl("attn_bwd", q, k, v, o, dout, lse, scale, mod, modarg, slopes,
+                       {}, {}, {}, false);
 }
 
 // attn_bwd on the split dK / dV kernels whatever the default is, so a test
@@ -1310,227 +1227,48 @@ std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, a
 std::vector<at::Tensor> attn_bwd_split(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                        at::Tensor dout, at::Tensor lse, double scale, long mod,
                                        long modarg, at::Tensor slopes) {
-  auto none = at::empty({0}, q.options());
-  return attn_bwd_impl(q, k, v, o, dout, lse, scale, mod, modarg, slopes,
-                       none, none.clone(), none.clone(), true);
+  return attn_bwd_impl("attn_bwd_split", q, k, v, o, dout, lse, scale, mod, modarg, slopes,
+                       {}, {}, {}, true);
 }
 
 // Backward of attn_fwd_blockmask (trainable flex attention): same device mask
 // tensors as the forward plus qrange, the per-kv-block transpose of range.
-// Always 8 waves/block: the mask tensors are laid out for 256-row blocks, so
-// MCDP_ATTN_BWD_NW does not apply here. bias (may be empty) gets no gradient.
+// bias (may be empty) gets no gradient.
 std::vector<at::Tensor> attn_bwd_blockmask(at::Tensor q, at::Tensor k, at::Tensor v,
                                            at::Tensor o, at::Tensor dout, at::Tensor lse,
                                            double scale, at::Tensor gran, at::Tensor bits,
                                            at::Tensor range, at::Tensor qrange,
                                            at::Tensor bias) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "attn_bwd_blockmask: bf16 only");
-  auto rs = [](at::Tensor& t) {
-    const int S = t.size(1), D = t.size(3);
-    if (!(t.stride(3) == 1 && t.stride(2) == D && t.stride(0) == (long)S * t.stride(1)))
-      t = t.contiguous();
-    return t.stride(1);
-  };
-  const long q_rs = rs(q), k_rs = rs(k), v_rs = rs(v), do_rs = rs(dout);
-  o = o.contiguous();
-  lse = lse.contiguous();
-  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Skv = k.size(1), Hkv = k.size(2);
-  TORCH_CHECK(Hq % Hkv == 0 && (D == 64 || D == 128),
-              "attn_bwd_blockmask: GQA needs Hq % Hkv == 0, head_dim 64 or 128");
-  TORCH_CHECK(k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16 &&
-              k.size(0) == B && k.size(3) == D && v.sizes() == k.sizes() &&
-              o.sizes() == q.sizes() && dout.sizes() == q.sizes(),
-              "attn_bwd_blockmask: q/k/v/o/dout shape mismatch");
-  TORCH_CHECK(dout.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16 &&
-              lse.scalar_type() == at::kFloat && lse.numel() == (long)B * Hq * Sq,
-              "attn_bwd_blockmask: o/dout bf16, lse f32 [B,H,S]");
-  TORCH_CHECK(gran.scalar_type() == at::kByte && bits.scalar_type() == at::kByte &&
-              range.scalar_type() == at::kInt && qrange.scalar_type() == at::kInt,
-              "blockmask tensor dtypes");
-  TORCH_CHECK(gran.is_cuda() && bits.is_cuda() && range.is_cuda() && qrange.is_cuda(),
-              "blockmask tensors must be on the GPU");
-  gran = gran.contiguous();
-  bits = bits.contiguous();
-  range = range.contiguous();
+  const char* who = "attn_bwd_blockmask";
+  at::Tensor dq, dk, dv;
+  AttnArgs a = bwd_args(who, q, k, v, o, dout, lse, scale, dq, dk, dv);
+  check_blockmask(who, a, q, gran, bits, range, bias);
+  TORCH_CHECK(qrange.scalar_type() == at::kInt && qrange.device() == q.device() &&
+              shape_is(qrange, a.B, a.Hq, cdiv(a.Skv, 256), 2),
+              who, ": qrange must be int32 [B,H,ceil(Skv/256),2] on q's GPU");
   qrange = qrange.contiguous();
-  constexpr int BLK = 8 * 32;  // q rows (dQ) / kv rows (dK, dV) per block
-  auto shape_is = [](const at::Tensor& t, long a, long b_, long c, long d) {
-    return t.dim() == 4 && t.size(0) == a && t.size(1) == b_ && t.size(2) == c && t.size(3) == d;
-  };
-  TORCH_CHECK(shape_is(gran, B, Hq, cdiv(Sq, 32), cdiv(Skv, 64)), "gran shape mismatch");
-  TORCH_CHECK(shape_is(bits, B, Hq, Sq, cdiv(Skv, 8)), "bits shape mismatch");
-  TORCH_CHECK(shape_is(range, B, Hq, cdiv(Sq, BLK), 2), "range shape mismatch");
-  TORCH_CHECK(shape_is(qrange, B, Hq, cdiv(Skv, BLK), 2), "qrange shape mismatch");
-  const bool has_bias = bias.numel() > 0;
-  if (has_bias) {
-    TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kBFloat16 &&
-                shape_is(bias, B, Hq, Sq, Skv), "bias must be bf16 [B,H,Sq,Skv]");
-    bias = bias.contiguous();
-  }
-  auto dq = at::empty({B, Sq, Hq, D}, q.options());
-  auto dk = at::empty({B, Skv, Hkv, D}, q.options());
-  auto dv = at::empty({B, Skv, Hkv, D}, q.options());
-  auto drow = at::empty({(long)B * Sq * Hq}, q.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentHIPStream();
-  {  // preprocess, as in attn_bwd_out
-    const long rows = (long)B * Sq * Hq;
-    const int rpw = WAVE / (D / 8);
-    const long grid = cdiv(rows, (long)(256 / WAVE) * rpw);
-    bwd_preprocess_kernel<<<grid, 256, 0, stream>>>(
-        reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-        reinterpret_cast<const __hip_bfloat16*>(o.data_ptr()),
-        drow.data_ptr<float>(), rows, D, do_rs, Hq);
-  }
-  dim3 gq(cdiv(Sq, BLK), Hq, B), gkv(cdiv(Skv, BLK), Hkv, B), block(8 * WAVE);
-  auto* qp = reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
-  auto* kp = reinterpret_cast<const __hip_bfloat16*>(k.data_ptr());
-  auto* vp = reinterpret_cast<const __hip_bfloat16*>(v.data_ptr());
-  auto* dop = reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr());
-  auto* bp = has_bias ? reinterpret_cast<const __hip_bfloat16*>(bias.data_ptr()) : nullptr;
-  const float* lp = lse.data_ptr<float>();
-  const float* drp = drow.data_ptr<float>();
-  const unsigned char* gp = gran.data_ptr<unsigned char>();
-  const unsigned char* bitp = bits.data_ptr<unsigned char>();
-  auto launch = [&](auto dtag) {
-    constexpr int DD = decltype(dtag)::value;
-    attn_bwd_dq_kernel<DD, MOD_BLOCKMASK, 8><<<gq, block, 0, stream>>>(
-        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()), nullptr,
-        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dq.stride(1),
-        gp, bitp, range.data_ptr<int>(), bp);
-    attn_bwd_dkv_kernel<DD, MOD_BLOCKMASK, true, 8><<<gkv, block, 0, stream>>>(
-        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()), nullptr,
-        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dk.stride(1),
-        gp, bitp, qrange.data_ptr<int>(), bp);
-    attn_bwd_dkv_kernel<DD, MOD_BLOCKMASK, false, 8><<<gkv, block, 0, stream>>>(
-        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()), nullptr,
-        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dv.stride(1),
-        gp, bitp, qrange.data_ptr<int>(), bp);
-  };
-  if (D == 64) launch(std::integral_constant<int, 64>{});
-  else launch(std::integral_constant<int, 128>{});
+  a.qrange = qrange.data_ptr<int>();
+  run_bwd<MOD_BLOCKMASK>(a, q, false);
   return {dq, dk, dv};
 }
 
 // Backward of attn_fwd_doc (document-masked packed sequences). doc_start /
-// doc_end are int32 [B, S]; dq/dk/dv may be empty (allocated here) or
-// row-strided views into a fused dQKV buffer, as in attn_bwd_out. Built for
-// 8 waves/block only, so MCDP_ATTN_BWD_NW does not apply here.
+// doc_end are int32 [B, S]; dq/dk/dv as in attn_bwd_out.
 std::vector<at::Tensor> attn_bwd_doc_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                          at::Tensor dout, at::Tensor lse, double scale,
                                          at::Tensor doc_start, at::Tensor doc_end,
                                          at::Tensor dq, at::Tensor dk, at::Tensor dv) {
-  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda() && o.is_cuda() && dout.is_cuda() &&
-              lse.is_cuda(), "attn_bwd_doc: GPU tensors only");
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 &&
-              v.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16 &&
-              dout.scalar_type() == at::kBFloat16, "attn_bwd_doc: bf16 only");
-  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "attn_bwd_doc: q/k/v must be [B,S,H,D]");
-  auto rs = [](at::Tensor& t) {
-    const int S = t.size(1), D = t.size(3);
-    if (!(t.stride(3) == 1 && t.stride(2) == D && t.stride(0) == (long)S * t.stride(1)))
-      t = t.contiguous();
-    return t.stride(1);
-  };
-  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Skv = k.size(1), Hkv = k.size(2);
-  TORCH_CHECK(Sq == Skv, "attn_bwd_doc: document mask is training-only (Sq == Skv), got ",
-              Sq, " vs ", Skv);
-  TORCH_CHECK(Hq % Hkv == 0 && (D == 64 || D == 128),
-              "attn_bwd_doc: GQA needs Hq % Hkv == 0, head_dim 64 or 128");
-  TORCH_CHECK(k.size(0) == B && k.size(3) == D && v.sizes() == k.sizes() &&
-              o.sizes() == q.sizes() && dout.sizes() == q.sizes(),
-              "attn_bwd_doc: q/k/v/o/dout shape mismatch");
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (long)B * Hq * Sq,
-              "attn_bwd_doc: lse must be f32 [B,H,S]");
-  auto check_doc = [&](const at::Tensor& t, const char* name) {
-    TORCH_CHECK(t.scalar_type() == at::kInt && t.is_contiguous() && t.dim() == 2 &&
-                t.size(0) == B && t.size(1) == Sq && t.device() == q.device(),
-                "attn_bwd_doc: ", name, " must be contiguous int32 [B,S] on q's device");
-  };
-  check_doc(doc_start, "doc_start");
-  check_doc(doc_end, "doc_end");
-  const long q_rs = rs(q), k_rs = rs(k), v_rs = rs(v), do_rs = rs(dout);
-  o = o.contiguous();
-  lse = lse.contiguous();
-  auto check_out = [&](at::Tensor& t, int S_, int H_) {
-    if (t.numel() == 0) {
-      t = at::empty({B, S_, H_, D}, q.options());
-    } else {
-      TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.dim() == 4 &&
-                      t.size(0) == B && t.size(1) == S_ && t.size(2) == H_ && t.size(3) == D &&
-                      t.stride(3) == 1 && t.stride(2) == D &&
-                      t.stride(0) == (long)S_ * t.stride(1),
-                  "attn_bwd_doc: bad out view");
-    }
-    return t.stride(1);
-  };
-  const long dq_rs = check_out(dq, Sq, Hq);
-  const long dk_rs = check_out(dk, Skv, Hkv);
-  const long dv_rs = check_out(dv, Skv, Hkv);
-  auto drow = at::empty({(long)B * Sq * Hq}, q.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentHIPStream();
-  {  // preprocess, as in attn_bwd_out
-    const long rows = (long)B * Sq * Hq;
-    const int rpw = WAVE / (D / 8);
-    const long grid = cdiv(rows, (long)(256 / WAVE) * rpw);
-    bwd_preprocess_kernel<<<grid, 256, 0, stream>>>(
-        reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-        reinterpret_cast<const __hip_bfloat16*>(o.data_ptr()),
-        drow.data_ptr<float>(), rows, D, do_rs, Hq);
-  }
-  constexpr int BLK = 8 * 32;  // q rows (dQ) / kv rows (dK, dV) per block
-  dim3 gq(cdiv(Sq, BLK), Hq, B), gkv(cdiv(Skv, BLK), Hkv, B), block(8 * WAVE);
-  auto* qp = reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
-  auto* kp = reinterpret_cast<const __hip_bfloat16*>(k.data_ptr());
-  auto* vp = reinterpret_cast<const __hip_bfloat16*>(v.data_ptr());
-  auto* dop = reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr());
-  const float* lp = lse.data_ptr<float>();
-  const float* drp = drow.data_ptr<float>();
-  const int* dsp = doc_start.data_ptr<int>();
-  const int* dep = doc_end.data_ptr<int>();
-  auto launch = [&](auto dtag) {
-    constexpr int DD = decltype(dtag)::value;
-    attn_bwd_dq_kernel<DD, MOD_DOCUMENT, 8><<<gq, block, 0, stream>>>(
-        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()), nullptr,
-        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dq_rs,
-        nullptr, nullptr, nullptr, nullptr, dsp);
-    // merged dK+dV at D=128, as in attn_bwd_out
-    if constexpr (DD == 128) {
-      if (!bwd_split()) {
-        attn_bwd_dkdv_kernel<DD, MOD_DOCUMENT><<<gkv, block, 0, stream>>>(
-            qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
-            reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()), nullptr,
-            B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dk_rs, dv_rs, dep);
-        return;
-      }
-    }
-    attn_bwd_dkv_kernel<DD, MOD_DOCUMENT, true, 8><<<gkv, block, 0, stream>>>(
-        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()), nullptr,
-        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dk_rs,
-        nullptr, nullptr, nullptr, nullptr, dep);
-    attn_bwd_dkv_kernel<DD, MOD_DOCUMENT, false, 8><<<gkv, block, 0, stream>>>(
-        qp, kp, vp, dop, lp, drp, reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()), nullptr,
-        B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs, do_rs, dv_rs,
-        nullptr, nullptr, nullptr, nullptr, dep);
-  };
-  if (D == 64) launch(std::integral_constant<int, 64>{});
-  else launch(std::integral_constant<int, 128>{});
+  const char* who = "attn_bwd_doc";
+  AttnArgs a = bwd_args(who, q, k, v, o, dout, lse, scale, dq, dk, dv);
+  a.doc_start = check_doc(who, a, q, doc_start, "doc_start");
+  a.doc_end = check_doc(who, a, q, doc_end, "doc_end");
+  run_bwd<MOD_DOCUMENT>(a, q, false);
   return {dq, dk, dv};
 }
 
 std::vector<at::Tensor> attn_bwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                      at::Tensor dout, at::Tensor lse, double scale,
                                      at::Tensor doc_start, at::Tensor doc_end) {
-  auto none = at::empty({0}, q.options());
-  return attn_bwd_doc_out(q, k, v, o, dout, lse, scale, doc_start, doc_end,
-                          none, none.clone(), none.clone());
+  return attn_bwd_doc_out(q, k, v, o, dout, lse, scale, doc_start, doc_end, {}, {}, {});
 }
 
-std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
-                                 at::Tensor dout, at::Tensor lse, double scale, long mod,
-                                 long modarg, at::Tensor slopes) {
-  auto none = at::empty({0}, q.options());
-  return attn_bwd_out(q, k, v, o, dout, lse, scale, mod, modarg, slopes,
-                      none, none.clone(), none.clone());
-}

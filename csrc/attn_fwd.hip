@@ -4,15 +4,16 @@
 // approach without tiling for now" — and simple_attention.py, flex_attention.py).
 //
 // Structure (gfx950), following the guide's 8-wave attention ladder:
-//   - NW waves/block, each wave owns 32 q rows (8 waves = 256 q rows share
-//     every K/V tile -> staging traffic amortized 8x),
+//   - 8 waves/block, each wave owns 32 q rows (256 q rows share every K/V
+//     tile -> staging traffic amortized 8x),
 //   - causal CU load balance: tile_map() rotates the q-tile index across a
 //     CU's successive blocks and (head-major layouts) pins each (b,h)'s
 //     blocks to one XCD (attn_common.h; fwd 433 -> 569 TF at the 1B shape),
 //   - cross-tile software pipeline: PV lags QK^T by one tile in a 3-slot
 //     LDS ring, so tile j's exp/psum/pack VALU shares a basic block (and
 //     the issue gaps) with tile j-1's PV MFMAs; branchless softmax tail,
-//   - KVB-row K/V tiles, ONE barrier per tile,
+//   - KVB-row K/V tiles (128 rows at D=64, 64 at D=128 and for every
+//     blockmask launch), ONE barrier per tile,
 //   - XOR-swizzled images (guide §6 Guideline 4: row-major D=128 bf16 read
 //     column-wise by a lane group is an up-to-16-way bank conflict, and +1
 //     padding does NOT fix it): K row-major [KVB][D] with element column
@@ -25,8 +26,7 @@
 //   - interior causal tiles take a mask-free fast path (wave-uniform branch),
 //   - T5 STATIC form only: one priority raise for the younger wave half
 //     (per-cluster setprio flips are scheduling fences and were keeping the
-//     softmax VALU out of the MFMA gaps; the sched_group_barrier interleave
-//     corrupts numerics and stays compiled-but-disabled — VAR bit 1),
+//     softmax VALU out of the MFMA gaps),
 //   - MOD_BLOCKMASK (K2): arbitrary mask_mod via device granule codes +
 //     packed keep-bits + per-block live kv ranges; optional additive bias
 //     stream for score_mod (ops/attention.py CompiledBlockMask),
@@ -35,9 +35,11 @@
 //     block's first document are skipped (ops/attention.py document_bounds),
 //   - causal/sliding-window tiles skipped at block level; GQA reads the
 //     shared KV head directly; BSHD layout, strided views accepted.
+// One configuration per (D, mod) is compiled: the wave count and tile size
+// above are the measured optima (profiles/attn_ladder.md).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "attn_common.h"
+#include "attn_launch.h"
 
 namespace {
 
@@ -45,8 +47,8 @@ constexpr int QPW = 32;  // q rows per wave
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
-template <int D, int MOD, int NW, int KVB, int VAR = 3>
-__global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
+template <int D, int MOD, int KVB>
+__global__ __launch_bounds__(8 * WAVE) void attn_fwd_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, __hip_bfloat16* __restrict__ o,
     float* __restrict__ lse, const float* __restrict__ slopes,
@@ -65,8 +67,7 @@ __global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
     // MOD_DOCUMENT only: doc_start int32 [B,Sq], first position of each
     // row's document (non-decreasing along s; same for every head)
     const int* __restrict__ doc_start = nullptr) {
-  static_assert(MOD != MOD_DOCUMENT || (NW == 8 && VAR == 1),
-                "document mask: default NW/VAR instantiations only");
+  constexpr int NW = 8;  // waves per block
   constexpr int TPB = NW * WAVE;
   constexpr int QPB = NW * QPW;
   constexpr int DBLK = D / 16;  // QK^T d-slots
@@ -234,7 +235,7 @@ __global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
   // arbitration on every segment; one static priority raise for it (and no
   // per-cluster flips: s_setprio is a scheduling fence that was keeping the
   // exp/pack VALU OUT of the PV MFMA issue gaps -- seen in the .s).
-  if ((VAR & 1) && NW == 8 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256)
+  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256)
     __builtin_amdgcn_s_setprio(1);
 
   // prologue: stage tile 0 into slot 0
@@ -398,19 +399,6 @@ __global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt) acc_to_afrag(p[kt], pa[kt][0], pa[kt][1]);
 
-    // sm-split (guide T19 + ladder rung 2b): the scheduler otherwise emits
-    // the whole exp/psum/pack VALU block AFTER the PV MFMAs (checked in the
-    // .s); these directives interleave ~24 VALU per 2 MFMAs so the VALU
-    // issues inside the matrix-pipe gaps.
-    if constexpr ((VAR & 2) != 0) {
-#pragma unroll
-      for (int g = 0; g < 8; ++g) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // DS_READ (V frags)
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, 24, 0); // VALU slice
-      }
-    }
-
     // o_acc rescale: strictly after PV(j-1), before PV(j) (T13 hazard);
     // skipped on the defer path (alpha == 1 there, the l-update above is
     // already folded in)
@@ -474,200 +462,63 @@ __global__ __launch_bounds__(NW* WAVE) void attn_fwd_kernel(
   }
 }
 
-int fwd_qpb() {  // q rows per block (needed by the host for grid sizing)
-  static int nw = []() {
-    const char* e = getenv("MCDP_ATTN_NW");
-    return e ? atoi(e) : 8;
-  }();
-  return nw * QPW;
+// The one forward launch: 8 waves per block of 256 q rows.
+template <int MOD>
+void run_fwd(const AttnArgs& a) {
+  constexpr int QPB = 8 * QPW;
+  const dim3 grid(cdiv(a.Sq, QPB), a.Hq, a.B), block(8 * WAVE);
+  auto stream = at::cuda::getCurrentHIPStream();
+  with_head_dim(a.D, [&](auto dtag) {
+    constexpr int D = decltype(dtag)::value;
+    // D=64 runs 128-row tiles: twice the MFMAs per barrier at the same
+    // occupancy (234 VGPR, no spill) — fwd 312 -> 363 TF at the 124M shape.
+    // D=128 has no VGPRs for them; the blockmask granules are 64 columns.
+    constexpr int KVB = (D == 64 && MOD != MOD_BLOCKMASK) ? 128 : 64;
+    attn_fwd_kernel<D, MOD, KVB><<<grid, block, 0, stream>>>(
+        a.q, a.k, a.v, a.o, a.lse, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv, a.scale, a.modarg,
+        a.q_rs, a.k_rs, a.v_rs, a.gran, a.bits, a.range, a.bias, a.doc_start);
+  });
 }
 
-template <int D, int MOD>
-void launch_fwd_cfg(dim3 grid, dim3 block, hipStream_t stream,
-                    const __hip_bfloat16* q, const __hip_bfloat16* k, const __hip_bfloat16* v,
-                    __hip_bfloat16* o, float* lse, const float* slopes,
-                    int B, int Sq, int Skv, int Hq, int Hkv, float scale, int modarg,
-                    long q_rs, long k_rs, long v_rs) {
-  const char* e = getenv("MCDP_ATTN_KVB");
-  // D=64 defaults to 128-row tiles: twice the MFMAs per barrier at the same
-  // occupancy (234 VGPR, no spill) — fwd 312 -> 363 TF at the 124M shape.
-  int kvb = e ? atoi(e) : (D == 64 ? 128 : 64);
-  if (kvb == 128 && D != 64) kvb = 64;  // KVB=128 is D=64-only (VGPR budget)
-  const int nw = fwd_qpb() / QPW;
-  static const int var = []() {
-    const char* e = getenv("MCDP_ATTN_FWD_VAR");
-    // default 1 = static-prio only. bit1 (sched_group_barrier interleave)
-    // CORRUPTS numerics (NaN via a poisoned cross-lane max; bisect
-    // gpurun_out/r2_call14.log: VAR 0/1 exact, VAR 2/3 NaN on every shape)
-    // — kept compiled for future debugging, not for use.
-    return e ? atoi(e) : 1;
-  }();
-#define LAUNCH(NW_, KVB_)                                                              \
-  do {                                                                                 \
-    if (var == 0)                                                                      \
-      attn_fwd_kernel<D, MOD, NW_, KVB_, 0><<<grid, block, 0, stream>>>(               \
-          q, k, v, o, lse, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs); \
-    else if (var == 1)                                                                 \
-      attn_fwd_kernel<D, MOD, NW_, KVB_, 1><<<grid, block, 0, stream>>>(               \
-          q, k, v, o, lse, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs); \
-    else if (var == 2)                                                                 \
-      attn_fwd_kernel<D, MOD, NW_, KVB_, 2><<<grid, block, 0, stream>>>(               \
-          q, k, v, o, lse, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs); \
-    else                                                                               \
-      attn_fwd_kernel<D, MOD, NW_, KVB_, 3><<<grid, block, 0, stream>>>(               \
-          q, k, v, o, lse, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs); \
-  } while (0)
-  if (nw == 8 && kvb == 64) LAUNCH(8, 64);
-  else if (nw == 8 && kvb == 32) LAUNCH(8, 32);
-  else if (nw == 4 && kvb == 64) LAUNCH(4, 64);
-  else if (nw == 4 && kvb == 32) LAUNCH(4, 32);
-  else if (nw == 16 && kvb == 64) LAUNCH(16, 64);
-  else if (nw == 8 && kvb == 128) {
-    if constexpr (D == 64) LAUNCH(8, 128);
-    else TORCH_CHECK(false, "attn_fwd: KVB=128 is D=64-only (LDS/VGPR budget)");
-  }
-  else TORCH_CHECK(false, "attn_fwd: unsupported NW/KVB ", nw, "/", kvb);
-#undef LAUNCH
-}
-
-template <int D>
-void launch_fwd(int mod, dim3 grid, dim3 block, hipStream_t stream,
-                const __hip_bfloat16* q, const __hip_bfloat16* k, const __hip_bfloat16* v,
-                __hip_bfloat16* o, float* lse, const float* slopes,
-                int B, int Sq, int Skv, int Hq, int Hkv, float scale, int modarg,
-                long q_rs, long k_rs, long v_rs) {
-  switch (mod) {
-    case MOD_NONE:
-      launch_fwd_cfg<D, MOD_NONE>(grid, block, stream, q, k, v, o, lse, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs);
-      break;
-    case MOD_CAUSAL:
-      launch_fwd_cfg<D, MOD_CAUSAL>(grid, block, stream, q, k, v, o, lse, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs);
-      break;
-    case MOD_SLIDING_WINDOW:
-      launch_fwd_cfg<D, MOD_SLIDING_WINDOW>(grid, block, stream, q, k, v, o, lse, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs);
-      break;
-    case MOD_PREFIX_LM:
-      launch_fwd_cfg<D, MOD_PREFIX_LM>(grid, block, stream, q, k, v, o, lse, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs);
-      break;
-    case MOD_ALIBI:
-      launch_fwd_cfg<D, MOD_ALIBI>(grid, block, stream, q, k, v, o, lse, slopes, B, Sq, Skv, Hq, Hkv, scale, modarg, q_rs, k_rs, v_rs);
-      break;
-    default:
-      TORCH_CHECK(false, "attn_fwd: unknown mod ", mod);
-  }
+// q/k/v checks shared by the three entry points, plus the outputs
+AttnArgs fwd_args(const char* who, at::Tensor& q, at::Tensor& k, at::Tensor& v, double scale,
+                  at::Tensor& o, at::Tensor& lse) {
+  AttnArgs a = check_qkv(who, q, k, v, scale);
+  o = at::empty({a.B, a.Sq, a.Hq, a.D}, q.options());
+  lse = at::empty({a.B, a.Hq, a.Sq}, q.options().dtype(at::kFloat));
+  a.o = bf16_out(o), a.lse = lse.data_ptr<float>();
+  return a;
 }
 
 }  // namespace
 
-static long bshd_row_stride(at::Tensor& t) {
-  // accept [B,S,H,D] views whose (h,d) inner block is contiguous (e.g. slices
-  // of the fused QKV projection); otherwise materialize.
-  const int S = t.size(1), H = t.size(2), D = t.size(3);
-  if (!(t.stride(3) == 1 && t.stride(2) == D && t.stride(0) == (long)S * t.stride(1)))
-    t = t.contiguous();
-  return t.stride(1);
-}
-
 std::vector<at::Tensor> attn_fwd_blockmask(at::Tensor q, at::Tensor k, at::Tensor v,
                                            double scale, at::Tensor gran, at::Tensor bits,
                                            at::Tensor range, at::Tensor bias) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "bf16 only");
-  const long q_rs = bshd_row_stride(q), k_rs = bshd_row_stride(k), v_rs = bshd_row_stride(v);
-  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Skv = k.size(1), Hkv = k.size(2);
-  TORCH_CHECK(Hq % Hkv == 0 && (D == 64 || D == 128));
-  TORCH_CHECK(gran.scalar_type() == at::kByte && bits.scalar_type() == at::kByte &&
-              range.scalar_type() == at::kInt, "blockmask tensor dtypes");
-  constexpr int QPB = 8 * 32;
-  TORCH_CHECK(range.size(2) == (Sq + QPB - 1) / QPB, "range shape mismatch");
-  auto o = at::empty({B, Sq, Hq, D}, q.options());
-  auto lse = at::empty({B, Hq, Sq}, q.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentHIPStream();
-  dim3 grid(cdiv(Sq, QPB), Hq, B), block(512);
-  const bool has_bias = bias.numel() > 0;
-  auto* bp = has_bias ? reinterpret_cast<const __hip_bfloat16*>(bias.data_ptr()) : nullptr;
-  auto launch1 = [&](auto dtag) {
-    constexpr int DD = decltype(dtag)::value;
-    attn_fwd_kernel<DD, MOD_BLOCKMASK, 8, 64, 1><<<grid, block, 0, stream>>>(
-        reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-        reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-        reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-        reinterpret_cast<__hip_bfloat16*>(o.data_ptr()), lse.data_ptr<float>(),
-        nullptr, B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs,
-        gran.data_ptr<unsigned char>(), bits.data_ptr<unsigned char>(),
-        range.data_ptr<int>(), bp);
-  };
-  if (D == 64) launch1(std::integral_constant<int, 64>{});
-  else launch1(std::integral_constant<int, 128>{});
+  at::Tensor o, lse;
+  AttnArgs a = fwd_args("attn_fwd_blockmask", q, k, v, scale, o, lse);
+  check_blockmask("attn_fwd_blockmask", a, q, gran, bits, range, bias);
+  run_fwd<MOD_BLOCKMASK>(a);
   return {o, lse};
 }
 
 // Document-masked forward (packed sequences). doc_start int32 [B, S]: first
-// position of the document each row belongs to. Runs the default
-// configuration only (8 waves, KVB 128 at D=64 / 64 at D=128, VAR 1), so
-// MCDP_ATTN_NW / MCDP_ATTN_KVB / MCDP_ATTN_FWD_VAR do not apply here.
+// position of the document each row belongs to.
 std::vector<at::Tensor> attn_fwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
                                      at::Tensor doc_start) {
-  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(), "attn_fwd_doc: GPU tensors only");
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 &&
-              v.scalar_type() == at::kBFloat16, "attn_fwd_doc: bf16 only");
-  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.sizes() == k.sizes(),
-              "attn_fwd_doc: q/k/v must be [B,S,H,D]");
-  const long q_rs = bshd_row_stride(q), k_rs = bshd_row_stride(k), v_rs = bshd_row_stride(v);
-  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Skv = k.size(1), Hkv = k.size(2);
-  TORCH_CHECK(Sq == Skv, "attn_fwd_doc: document mask is training-only (Sq == Skv), got ",
-              Sq, " vs ", Skv);
-  TORCH_CHECK(k.size(0) == B && k.size(3) == D, "attn_fwd_doc: q/k shape mismatch");
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
-  TORCH_CHECK(D == 64 || D == 128, "attn_fwd_doc: head_dim must be 64 or 128, got ", D);
-  TORCH_CHECK(doc_start.scalar_type() == at::kInt && doc_start.is_contiguous() &&
-              doc_start.dim() == 2 && doc_start.size(0) == B && doc_start.size(1) == Sq &&
-              doc_start.device() == q.device(),
-              "attn_fwd_doc: doc_start must be contiguous int32 [B,S] on q's device");
-  auto o = at::empty({B, Sq, Hq, D}, q.options());
-  auto lse = at::empty({B, Hq, Sq}, q.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentHIPStream();
-  constexpr int QPB = 8 * QPW;
-  dim3 grid(cdiv(Sq, QPB), Hq, B), block(8 * WAVE);
-  auto launch1 = [&](auto dtag) {
-    constexpr int DD = decltype(dtag)::value;
-    attn_fwd_kernel<DD, MOD_DOCUMENT, 8, (DD == 64 ? 128 : 64), 1><<<grid, block, 0, stream>>>(
-        reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-        reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-        reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-        reinterpret_cast<__hip_bfloat16*>(o.data_ptr()), lse.data_ptr<float>(),
-        nullptr, B, Sq, Skv, Hq, Hkv, (float)scale, 0, q_rs, k_rs, v_rs,
-        nullptr, nullptr, nullptr, nullptr, doc_start.data_ptr<int>());
-  };
-  if (D == 64) launch1(std::integral_constant<int, 64>{});
-  else launch1(std::integral_constant<int, 128>{});
+  at::Tensor o, lse;
+  AttnArgs a = fwd_args("attn_fwd_doc", q, k, v, scale, o, lse);
+  a.doc_start = check_doc("attn_fwd_doc", a, q, doc_start, "doc_start");
+  run_fwd<MOD_DOCUMENT>(a);
   return {o, lse};
 }
 
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
                                  long mod, long modarg, at::Tensor slopes) {
-  TORCH_CHECK(q.is_cuda());
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "attn_fwd: bf16 only");
-  const long q_rs = bshd_row_stride(q), k_rs = bshd_row_stride(k), v_rs = bshd_row_stride(v);
-  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Skv = k.size(1), Hkv = k.size(2);
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
-  TORCH_CHECK(D == 64 || D == 128, "attn_fwd: head_dim must be 64 or 128, got ", D);
-  auto o = at::empty({B, Sq, Hq, D}, q.options());
-  auto lse = at::empty({B, Hq, Sq}, q.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentHIPStream();
-  const int qpb = fwd_qpb();
-  dim3 grid(cdiv(Sq, qpb), Hq, B);
-  dim3 block(qpb / QPW * WAVE);
-  const float* sl = slopes.numel() > 0 ? slopes.data_ptr<float>() : nullptr;
-  auto* qp = reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
-  auto* kp = reinterpret_cast<const __hip_bfloat16*>(k.data_ptr());
-  auto* vp = reinterpret_cast<const __hip_bfloat16*>(v.data_ptr());
-  auto* op = reinterpret_cast<__hip_bfloat16*>(o.data_ptr());
-  if (D == 64)
-    launch_fwd<64>((int)mod, grid, block, stream, qp, kp, vp, op, lse.data_ptr<float>(), sl, B, Sq, Skv, Hq, Hkv, (float)scale, (int)modarg, q_rs, k_rs, v_rs);
-  else
-    launch_fwd<128>((int)mod, grid, block, stream, qp, kp, vp, op, lse.data_ptr<float>(), sl, B, Sq, Skv, Hq, Hkv, (float)scale, (int)modarg, q_rs, k_rs, v_rs);
+  at::Tensor o, lse;
+  AttnArgs a = fwd_args("attn_fwd", q, k, v, scale, o, lse);
+  check_slopes("attn_fwd", a, mod, slopes, q);
+  a.modarg = (int)modarg;
+  with_mod("attn_fwd", mod, [&](auto mtag) { run_fwd<decltype(mtag)::value>(a); });
   return {o, lse};
 }

@@ -334,9 +334,6 @@ def flash_attention(
         ``doc_start <= s < doc_end``); the kernels clamp what they use as an
         address or loop bound, so a bad tensor gives wrong numbers, not a
         fault.
-      * The kernel path is built for the default launch configuration only:
-        MCDP_ATTN_NW, MCDP_ATTN_KVB, MCDP_ATTN_FWD_VAR and MCDP_ATTN_BWD_NW
-        do not apply to it.
       * RoPE needs no per-document position reset: scores depend on
         q_pos - k_pos only.
     """
@@ -479,8 +476,8 @@ def flex_attention(
       * ``score_mod`` is evaluated ONCE into a bf16 [B, H, S, KV] bias that
         is kept for the backward: O(S^2) memory, and the bias (e.g. a
         learned table) gets no gradient on this path.
-      * The mask tensors are laid out for 256-row blocks, so the backward
-        always runs 8 waves per block; MCDP_ATTN_BWD_NW does not apply.
+      * The mask tensors are laid out for the kernels' 256-row blocks
+        (8 waves per block, forward and backward).
     """
     if isinstance(block_mask, CompiledBlockMask):
         return _flex_blockmask(q, k, v, block_mask, score_mod, scale)

@@ -318,6 +318,44 @@ def test_attn_bwd_gpu(ext, case):
         assert err < 0.05 * max(ref_mag, 1.0), f"{name} max err {err} (ref mag {ref_mag}) case {case}"
 
 
+def test_host_checks_reject_bad_attention_args(ext):
+    """Every attention entry point validates all of its tensors before any
+    launch. Each bad tensor below is at least as many bytes as the right one,
+    so a launch that skipped the check would still stay inside the allocations."""
+    B, S, H, D = 1, 128, 2, 64
+    scale = 1.0 / math.sqrt(D)
+    torch.manual_seed(0)
+    mk = lambda: torch.randn(B, S, H, D, device=dev(), dtype=torch.bfloat16)
+    q, k, v, dout = mk(), mk(), mk(), mk()
+    none = torch.empty(0, device=dev())
+    o, lse = ext.attn_fwd(q, k, v, scale, 1, 0, none)
+    good = ext.attn_bwd(q, k, v, o, dout, lse, scale, 1, 0, none)
+
+    bad_slopes = torch.ones(H, device=dev(), dtype=torch.float64)
+    empty = torch.empty(0, device=dev(), dtype=torch.bfloat16)
+    rejected = [
+        lambda: ext.attn_fwd(q, k.half(), v, scale, 1, 0, none),           # k fp16
+        lambda: ext.attn_bwd(q, k.half(), v, o, dout, lse, scale, 1, 0, none),
+        lambda: ext.attn_bwd(q, k, v, o, dout, lse.double(), scale, 1, 0, none),  # lse f64
+        lambda: ext.attn_bwd(q, k, v, o, dout.half(), lse, scale, 1, 0, none),    # dout fp16
+        lambda: ext.attn_bwd_out(q, k, v, o, dout, lse, scale, 1, 0, none,        # dq view f32
+                                 torch.empty(B, S, H, D, device=dev()), empty, empty.clone()),
+        lambda: ext.attn_fwd(q, k, v, scale, 4, 0, bad_slopes),             # slopes f64
+        lambda: ext.attn_bwd(q, k, v, o, dout, lse, scale, 4, 0, bad_slopes),
+        lambda: ext.attn_fwd(q, k, v, scale, 17, 0, none),                  # unknown mod
+        lambda: ext.attn_bwd(q, k, v, o, dout, lse, scale, 17, 0, none),
+    ]
+    for i, call in enumerate(rejected):
+        with pytest.raises(RuntimeError):
+            call()
+            pytest.fail(f"bad call {i} was accepted")
+
+    # nothing was launched or left behind: the good path still gives the same bits
+    again = ext.attn_bwd(q, k, v, o, dout, lse, scale, 1, 0, none)
+    for name, a, b in zip(("dq", "dk", "dv"), good, again):
+        assert torch.equal(a, b), name
+
+
 def test_fused_qkv_rope_attention_matches_composition(ext):
     """Fused qkv->RoPE->attention autograd node vs the op composition
     (incl. dQKV written in place by attn_bwd_out/rope_fwd_out)."""
