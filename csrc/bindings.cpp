@@ -11,6 +11,15 @@ at::Tensor rope_fwd(at::Tensor x, at::Tensor cost, at::Tensor sint, bool traditi
                     long offset, bool conj);
 at::Tensor rope_fwd_out(at::Tensor x, at::Tensor cost, at::Tensor sint, bool traditional,
                         long offset, bool conj, at::Tensor y);
+// qknorm_rope.hip
+std::vector<at::Tensor> qknorm_rope_fwd(at::Tensor x, long Hq, at::Tensor wq, at::Tensor wk,
+                                        at::Tensor cost, at::Tensor sint, bool traditional,
+                                        long offset, double eps);
+at::Tensor qknorm_rope_bwd(at::Tensor g_r, at::Tensor x, at::Tensor rstd, long Hq,
+                           at::Tensor wq, at::Tensor wk, at::Tensor cost, at::Tensor sint,
+                           bool traditional, long offset, at::Tensor dx);
+void qknorm_rope_decode_(at::Tensor x, long Hq, at::Tensor wq, at::Tensor wk, at::Tensor cost,
+                         at::Tensor sint, bool traditional, at::Tensor pos, double eps);
 // swiglu.hip
 at::Tensor swiglu_fwd(at::Tensor gu);
 std::vector<at::Tensor> swiglu_fwd_amax(at::Tensor gu, bool with_amax);
@@ -105,6 +114,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_bwd_add", &rmsnorm_bwd_add, "RMSNorm bwd with fused grad add (dx, dw)");
   m.def("rope_fwd", &rope_fwd, "RoPE apply (conj=true for backward)");
   m.def("rope_fwd_out", &rope_fwd_out, "RoPE apply into a strided out view");
+  m.def("qknorm_rope_fwd", &qknorm_rope_fwd,
+        "fused per-head QK RMSNorm + RoPE over the q|k heads of a [B,S,H,D] view (y, rstd)");
+  m.def("qknorm_rope_bwd", &qknorm_rope_bwd,
+        "backward of qknorm_rope_fwd into a strided dx view; returns dw [2,D] (q, k)");
+  m.def("qknorm_rope_decode_", &qknorm_rope_decode_,
+        "in-place QK-norm + RoPE at device position");
   m.def("swiglu_fwd", &swiglu_fwd, "SwiGLU forward");
   m.def("swiglu_fwd_amax", &swiglu_fwd_amax, "swiglu fwd emitting |out| amax bits");
   m.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward");

@@ -54,12 +54,22 @@ class StaticLayerCache:
         Hq, Hkv, D = attn.n_heads, attn.n_kv_heads, attn.head_dim
         kc, vc = ow.k[self.idx], ow.v[self.idx]
         trad = attn.args.rope_traditional
+        qk_norm = getattr(attn.args, "qk_norm", False)
+        eps = attn.args.rms_norm_eps
 
         if use_hip(qkv, dtypes=(torch.bfloat16,)):
             ext = get_ext()
             qkv = qkv.contiguous()
             qk = qkv[..., : (Hq + Hkv) * D].view(B, 1, Hq + Hkv, D)
-            if qk.is_contiguous():  # B == 1: q and k are ADJACENT in the fused
+            if qk_norm:
+                # QK-norm + RoPE in place on the batch-strided q|k view: one
+                # launch for any B, same per-row arithmetic as the prefill
+                # kernel (bit-identical at the same position)
+                ext.qknorm_rope_decode_(qk, Hq, attn.q_norm.weight, attn.k_norm.weight,
+                                        ow.cos, ow.sin, trad, ow.pos, eps)
+                q = qkv[..., : Hq * D].view(B, 1, Hq, D)
+                k = qkv[..., Hq * D : (Hq + Hkv) * D].view(B, 1, Hkv, D).contiguous()
+            elif qk.is_contiguous():  # B == 1: q and k are ADJACENT in the fused
                 # projection — one in-place RoPE launch covers both
                 ext.rope_decode_(qk, ow.cos, ow.sin, trad, ow.pos)
                 q = qkv[..., : Hq * D].view(B, 1, Hq, D)
@@ -88,6 +98,11 @@ class StaticLayerCache:
         from ..ops.rope import rope_ref
 
         p = int(ow.pos.item())
+        if qk_norm:
+            from ..ops.rmsnorm import rms_norm_ref
+
+            q = rms_norm_ref(q, attn.q_norm.weight, eps)
+            k = rms_norm_ref(k, attn.k_norm.weight, eps)
         q = rope_ref(q, ow.cos, ow.sin, trad, offset=p)
         k = rope_ref(k, ow.cos, ow.sin, trad, offset=p)
         if ow.kv_bits == 8:

@@ -32,6 +32,7 @@ from ..ops.attention import (
 from ..ops.gemv import FastLinear, linear_fast
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
 from ..parallel.tp import copy_to_tp, gather_sp, reduce_from_tp, scatter_sp, tp_group
+from ..ops.qk_norm import qk_norm_rope
 from ..ops.rope import RopeTable, apply_rope
 from ..ops.swiglu import swiglu
 
@@ -58,6 +59,9 @@ class ModelArgs:
     attention_window: Optional[int] = None  # sliding-window size (flex)
     attention_prefix_len: Optional[int] = None  # prefix-LM split (flex)
     use_alibi: bool = False
+    # per-head RMSNorm over head_dim on q and k before RoPE (OLMo-2 / Qwen3 /
+    # Gemma-3 style; ops/qk_norm.py)
+    qk_norm: bool = False
     fp8: bool = False  # opt-in e4m3 GEMMs for the block projections (ops/fp8.py)
     router_aux_loss_coef: float = 0.01  # MoE load-balance loss weight
     # MoE knobs exist in the reference config (models/llama.py:40-41) but no
@@ -102,6 +106,7 @@ class ModelArgs:
             attention_window=attn.get("window"),
             attention_prefix_len=attn.get("prefix_len"),
             use_alibi=bool(attn.get("alibi", False)),
+            qk_norm=bool(attn.get("qk_norm", False)),
             num_local_experts=int(dims.get("num_local_experts", 0) or 0),
             num_experts_per_tok=int(dims.get("num_experts_per_tok", 0) or 0),
             moe_capacity_factor=float(dims.get("moe_capacity_factor", 0.0) or 0.0),
@@ -151,6 +156,11 @@ class Attention(nn.Module):
         self.wo = FastLinear(self.n_heads * self.head_dim, args.hidden_size, bias=args.attention_bias)
         self.wqkv.fp8 = self.wo.fp8 = args.fp8
         self.rope_table = rope_table
+        if args.qk_norm:
+            # one [head_dim] weight each, shared by all heads ("norm" in the
+            # name: no weight decay, AdamW side of the hybrid optimizer)
+            self.q_norm = RMSNorm(self.head_dim, eps=args.rms_norm_eps)
+            self.k_norm = RMSNorm(self.head_dim, eps=args.rms_norm_eps)
         self.flex_mask = None  # set through Model.set_flex_mask
         if args.use_alibi:
             slopes = torch.tensor(
@@ -159,6 +169,14 @@ class Attention(nn.Module):
             self.register_buffer("alibi_slopes", slopes, persistent=False)
         else:
             self.alibi_slopes = None
+
+    def _rope(self, q: torch.Tensor, k: torch.Tensor, cos, sin, offset: int):
+        """RoPE on q and k, behind the per-head QK-norm when the model has one."""
+        trad = self.args.rope_traditional
+        if self.args.qk_norm:
+            return qk_norm_rope(q, k, self.q_norm.weight, self.k_norm.weight, cos, sin,
+                                self.args.rms_norm_eps, trad, offset)
+        return apply_rope(q, cos, sin, trad, offset), apply_rope(k, cos, sin, trad, offset)
 
     def forward(self, x: torch.Tensor, cache: Optional[KVCache] = None,
                 doc_start: Optional[torch.Tensor] = None,
@@ -201,10 +219,8 @@ class Attention(nn.Module):
                 dim=-1,
             )
             cos, sin = self.rope_table.get(S, x.device, 0)
-            q = apply_rope(q.view(B, S, self.n_heads, self.head_dim), cos, sin,
-                           self.args.rope_traditional, 0)
-            k = apply_rope(k.view(B, S, self.n_kv_heads, self.head_dim), cos, sin,
-                           self.args.rope_traditional, 0)
+            q, k = self._rope(q.view(B, S, self.n_heads, self.head_dim),
+                              k.view(B, S, self.n_kv_heads, self.head_dim), cos, sin, 0)
             v = v.view(B, S, self.n_kv_heads, self.head_dim)
             if isinstance(self.flex_mask, CompiledBlockMask):
                 o = flex_attention(q, k, v, block_mask=self.flex_mask, scale=self.scale)
@@ -227,6 +243,9 @@ class Attention(nn.Module):
                 prefix_len=self.args.attention_prefix_len if atype == "flex" else None,
                 alibi_slopes=self.alibi_slopes if self.args.use_alibi else None,
                 doc_start=doc_start, doc_end=doc_end,
+                q_norm_weight=self.q_norm.weight if self.args.qk_norm else None,
+                k_norm_weight=self.k_norm.weight if self.args.qk_norm else None,
+                norm_eps=self.args.rms_norm_eps,
             )
             out = self.wo(o.reshape(B, S, -1))
             if getattr(self, "_sp", False) and self.training:
@@ -247,8 +266,7 @@ class Attention(nn.Module):
 
         offset = cache.offset if cache is not None else 0
         cos, sin = self.rope_table.get(S, x.device, offset)
-        q = apply_rope(q, cos, sin, self.args.rope_traditional, offset)
-        k = apply_rope(k, cos, sin, self.args.rope_traditional, offset)
+        q, k = self._rope(q, k, cos, sin, offset)
 
         if cache is not None:
             k, v = cache.update(k.contiguous(), v.contiguous())

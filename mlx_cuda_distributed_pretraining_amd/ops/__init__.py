@@ -1,5 +1,6 @@
 from .rmsnorm import RMSNorm, rms_norm, rms_norm_ref
 from .rope import RopeTable, apply_rope, rope_ref
+from .qk_norm import qk_norm_rope
 from .swiglu import swiglu, swiglu_ref
 from .cross_entropy import fused_cross_entropy, cross_entropy_ref
 from .attention import (
@@ -19,6 +20,7 @@ from ._ext import get_ext, require_ext
 __all__ = [
     "RMSNorm", "rms_norm", "rms_norm_ref",
     "RopeTable", "apply_rope", "rope_ref",
+    "qk_norm_rope",
     "swiglu", "swiglu_ref",
     "fused_cross_entropy", "cross_entropy_ref",
     "BlockMask", "attention_ref", "create_block_mask", "document_bounds",

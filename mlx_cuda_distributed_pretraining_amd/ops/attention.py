@@ -406,6 +406,73 @@ class _RopeAttnQKVFn(torch.autograd.Function):
         return (dqkv,) + (None,) * 13
 
 
+class _QKNormRopeAttnQKVFn(torch.autograd.Function):
+    """_RopeAttnQKVFn with per-head QK-norm: fused qkv -> RMSNorm(q,k heads) ->
+    RoPE -> flash attention, HIP path only.
+
+    Forward: ONE qknorm_rope_fwd launch covers the q and k heads (they are
+    adjacent in a token row; h < Hq picks the q weight) and replaces the two
+    RoPE launches; the attention kernels run unchanged on its output. Backward:
+    the attention backward writes dV into the dqkv buffer and the rotated
+    dQ/dK side by side into one scratch tensor, then ONE qknorm_rope_bwd launch
+    un-rotates, applies the norm backward from the saved qkv and the fp32 rstd,
+    writes the dq|dk slices of dqkv and returns both weight gradients."""
+
+    @staticmethod
+    def forward(ctx, qkv, q_w, k_w, cos, sin, Hq, Hkv, D, eps, traditional, causal, scale,
+                window, prefix_len, alibi_slopes, doc_start=None, doc_end=None):
+        B, S, _ = qkv.shape
+        scale = scale if scale is not None else 1.0 / math.sqrt(D)
+        x = qkv[..., : (Hq + Hkv) * D].view(B, S, Hq + Hkv, D)
+        v = qkv[..., (Hq + Hkv) * D :].view(B, S, Hkv, D)
+        from .qk_norm import kernel_weight
+
+        ext = get_ext()
+        wq = kernel_weight(q_w, qkv.dtype)
+        wk = kernel_weight(k_w, qkv.dtype)
+        y, rstd = ext.qknorm_rope_fwd(x, Hq, wq, wk, cos, sin, traditional, 0, eps)
+        qr, kr = y[:, :, :Hq], y[:, :, Hq:]
+        mod = _mods_to_code(causal, window, prefix_len, alibi_slopes is not None)
+        modarg = int(window if window is not None
+                     else (prefix_len if prefix_len is not None else 0))
+        slopes = (alibi_slopes.float().contiguous() if alibi_slopes is not None
+                  else torch.empty(0, dtype=torch.float32, device=qkv.device))
+        ctx.doc = doc_start is not None
+        if ctx.doc:
+            o, lse = ext.attn_fwd_doc(qr, kr, v, scale, doc_start)
+            ctx.save_for_backward(qkv, y, rstd, wq, wk, o, lse, cos, sin, slopes,
+                                  doc_start, doc_end)
+        else:
+            o, lse = ext.attn_fwd(qr, kr, v, scale, mod, modarg, slopes)
+            ctx.save_for_backward(qkv, y, rstd, wq, wk, o, lse, cos, sin, slopes)
+        ctx.meta = (Hq, Hkv, D, traditional, scale, mod, modarg, q_w.dtype, k_w.dtype)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, y, rstd, wq, wk, o, lse, cos, sin, slopes = ctx.saved_tensors[:10]
+        Hq, Hkv, D, traditional, scale, mod, modarg, qw_dtype, kw_dtype = ctx.meta
+        B, S, _ = qkv.shape
+        ext = get_ext()
+        x = qkv[..., : (Hq + Hkv) * D].view(B, S, Hq + Hkv, D)
+        v = qkv[..., (Hq + Hkv) * D :].view(B, S, Hkv, D)
+        qr, kr = y[:, :, :Hq], y[:, :, Hq:]
+        dqkv = torch.empty_like(qkv)
+        dqk_t = dqkv[..., : (Hq + Hkv) * D].view(B, S, Hq + Hkv, D)
+        dv_t = dqkv[..., (Hq + Hkv) * D :].view(B, S, Hkv, D)
+        g_r = torch.empty_like(y)  # rotated dq | dk
+        dq_r, dk_r = g_r[:, :, :Hq], g_r[:, :, Hq:]
+        if ctx.doc:
+            doc_start, doc_end = ctx.saved_tensors[10:]
+            ext.attn_bwd_doc_out(qr, kr, v, o, do, lse, scale, doc_start, doc_end,
+                                 dq_r, dk_r, dv_t)
+        else:
+            ext.attn_bwd_out(qr, kr, v, o, do, lse, scale, mod, modarg, slopes,
+                             dq_r, dk_r, dv_t)
+        dw = ext.qknorm_rope_bwd(g_r, x, rstd, Hq, wq, wk, cos, sin, traditional, 0, dqk_t)
+        return (dqkv, dw[0].to(qw_dtype), dw[1].to(kw_dtype)) + (None,) * 14
+
+
 def rope_flash_attention_qkv(
     qkv: torch.Tensor,
     cos: torch.Tensor,
@@ -421,14 +488,41 @@ def rope_flash_attention_qkv(
     alibi_slopes: Optional[torch.Tensor] = None,
     doc_start: Optional[torch.Tensor] = None,
     doc_end: Optional[torch.Tensor] = None,
+    q_norm_weight: Optional[torch.Tensor] = None,
+    k_norm_weight: Optional[torch.Tensor] = None,
+    norm_eps: float = 1e-5,
 ) -> torch.Tensor:
     """qkv: [B, S, (Hq+2*Hkv)*D] fused projection output -> o [B, S, Hq, D].
 
     HIP fast path (one fused autograd node, no grad cat); CPU falls back to
     the differentiable composition of the same ops. ``doc_start`` /
-    ``doc_end``: packed-sequence document mask, see ``flash_attention``."""
+    ``doc_end``: packed-sequence document mask, see ``flash_attention``.
+
+    ``q_norm_weight`` / ``k_norm_weight`` (``[head_dim]``, both or neither):
+    per-head QK-norm before RoPE, see ``ops.qk_norm``. With both ``None`` the
+    path is the plain RoPE + attention one."""
     B, S, _ = qkv.shape
     _check_doc_args(doc_start, doc_end, causal, window, prefix_len, alibi_slopes, S, S)
+    if (q_norm_weight is None) != (k_norm_weight is None):
+        raise ValueError("QK-norm needs both q_norm_weight and k_norm_weight")
+    if q_norm_weight is not None:
+        from .qk_norm import HIP_HEAD_DIMS, qk_norm_rope
+
+        Hq, Hkv, D = n_heads, n_kv_heads, head_dim
+        if D in HIP_HEAD_DIMS and use_hip(qkv, dtypes=(torch.bfloat16,)):
+            if doc_start is not None:
+                doc_start, doc_end = _doc_pair(doc_start, doc_end, B, S, qkv.device)
+            return _QKNormRopeAttnQKVFn.apply(
+                qkv, q_norm_weight, k_norm_weight, cos, sin, Hq, Hkv, D, float(norm_eps),
+                traditional, causal, scale, window, prefix_len, alibi_slopes,
+                doc_start, doc_end)
+        q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+        q, k = qk_norm_rope(q.view(B, S, Hq, D), k.view(B, S, Hkv, D), q_norm_weight,
+                            k_norm_weight, cos, sin, norm_eps, traditional, 0)
+        return flash_attention(q, k, v.view(B, S, Hkv, D), causal=causal, scale=scale,
+                               window=window, prefix_len=prefix_len,
+                               alibi_slopes=alibi_slopes, doc_start=doc_start,
+                               doc_end=doc_end)
     if use_hip(qkv, dtypes=(torch.bfloat16,)):
         if doc_start is not None:
             doc_start, doc_end = _doc_pair(doc_start, doc_end, B, S, qkv.device)

@@ -406,6 +406,14 @@ def apply_tensor_parallel(model, rank: int, world: int,
     if world <= 1:
         return
     args = model.args
+    if getattr(args, "qk_norm", False):
+        raise NotImplementedError(
+            "tensor/sequence parallelism with qk_norm is not supported yet: the "
+            "[head_dim] q_norm/k_norm weights are replicated while the heads are "
+            "sharded, so every rank holds a partial gradient that needs an "
+            "all-reduce over the TP group (ROADMAP) - train qk_norm models with "
+            "data parallelism"
+        )
     if args.num_heads % world or args.num_kv_heads % world:
         raise ValueError(
             f"TP degree {world} must divide num_heads={args.num_heads} and "

@@ -63,6 +63,9 @@ def fused_to_hf_state(state: Dict[str, torch.Tensor], args: ModelArgs) -> Dict[s
             elif rest in ("attention.wo.weight", "attention.wo.bias"):
                 kind = rest.rsplit(".", 1)[1]
                 out[f"{pre}.self_attn.o_proj.{kind}"] = t
+            elif rest in ("attention.q_norm.weight", "attention.k_norm.weight"):
+                # per-head QK-norm (model.attention.qk_norm): Qwen3 naming
+                out[f"{pre}.self_attn.{parts[3]}.weight"] = t
             elif rest in ("mlp.w_gate_up.weight", "mlp.w_gate_up.bias"):
                 kind = rest.rsplit(".", 1)[1]
                 g, u = t.split([inter, inter], dim=0)
@@ -76,9 +79,12 @@ def fused_to_hf_state(state: Dict[str, torch.Tensor], args: ModelArgs) -> Dict[s
 
 
 def hf_config_from(config: Config, args: ModelArgs) -> Dict:
+    # Llama + per-head QK RMSNorm before RoPE + explicit head_dim is the Qwen3
+    # architecture; without QK-norm the export stays plain Llama.
+    qk_norm = getattr(args, "qk_norm", False)
     return {
-        "architectures": ["LlamaForCausalLM"],
-        "model_type": "llama",
+        "architectures": ["Qwen3ForCausalLM" if qk_norm else "LlamaForCausalLM"],
+        "model_type": "qwen3" if qk_norm else "llama",
         "hidden_size": args.hidden_size,
         "intermediate_size": args.intermediate_size,
         "num_hidden_layers": args.num_layers,
