@@ -1207,19 +1207,17 @@ std::vector<at::Tensor> attn_bwd_impl(const char* who, at::Tensor q, at::Tensor 
 
 }  // namespace
 
-std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
-                                     at::Tensor dout, at::Tensor lse, double scale, long mod,
-                                     long modarg, at::Tensor slopes,
-                                     at::Tensor dq, at::Tensor dk, at::Tensor dv) {
-  return attn_bwd_impl("attn_bwd_out", q, k, v, o, dout, lse, scale, mod, modarg, slopes,
-                       dq, dk, dv, false);
-}
+// dq/dk/dv: absent or empty -> allocated here; else row-strided out views
+// (slices of a fused dQKV grad buffer) that the kernels write in place.
+using OptTensor = c10::optional<at::Tensor>;
 
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                  at::Tensor dout, at::Tensor lse, double scale, long mod,
-                                 long modarg, at::Tensor slopes) {
+                                 long modarg, at::Tensor slopes,
+                                 OptTensor dq, OptTensor dk, OptTensor dv) {
   return attn_bwd_impl("attn_bwd", q, k, v, o, dout, lse, scale, mod, modarg, slopes,
-                       {}, {}, {}, false);
+                       dq.value_or(at::Tensor()), dk.value_or(at::Tensor()),
+                       dv.value_or(at::Tensor()), false);
 }
 
 // attn_bwd on the split dK / dV kernels whatever the default is, so a test
@@ -1253,22 +1251,17 @@ std::vector<at::Tensor> attn_bwd_blockmask(at::Tensor q, at::Tensor k, at::Tenso
 }
 
 // Backward of attn_fwd_doc (document-masked packed sequences). doc_start /
-// doc_end are int32 [B, S]; dq/dk/dv as in attn_bwd_out.
-std::vector<at::Tensor> attn_bwd_doc_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
-                                         at::Tensor dout, at::Tensor lse, double scale,
-                                         at::Tensor doc_start, at::Tensor doc_end,
-                                         at::Tensor dq, at::Tensor dk, at::Tensor dv) {
+// doc_end are int32 [B, S]; dq/dk/dv as in attn_bwd.
+std::vector<at::Tensor> attn_bwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                     at::Tensor dout, at::Tensor lse, double scale,
+                                     at::Tensor doc_start, at::Tensor doc_end,
+                                     OptTensor dq_, OptTensor dk_, OptTensor dv_) {
   const char* who = "attn_bwd_doc";
+  at::Tensor dq = dq_.value_or(at::Tensor()), dk = dk_.value_or(at::Tensor()),
+             dv = dv_.value_or(at::Tensor());
   AttnArgs a = bwd_args(who, q, k, v, o, dout, lse, scale, dq, dk, dv);
   a.doc_start = check_doc(who, a, q, doc_start, "doc_start");
   a.doc_end = check_doc(who, a, q, doc_end, "doc_end");
   run_bwd<MOD_DOCUMENT>(a, q, false);
   return {dq, dk, dv};
 }
-
-std::vector<at::Tensor> attn_bwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
-                                     at::Tensor dout, at::Tensor lse, double scale,
-                                     at::Tensor doc_start, at::Tensor doc_end) {
-  return attn_bwd_doc_out(q, k, v, o, dout, lse, scale, doc_start, doc_end, {}, {}, {});
-}
-

@@ -54,16 +54,14 @@ std::vector<at::Tensor> attn_fwd_blockmask(at::Tensor q, at::Tensor k, at::Tenso
                                            at::Tensor range, at::Tensor bias);
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
                                  long mod, long modarg, at::Tensor slopes);
+using OptTensor = c10::optional<at::Tensor>;  // dq/dk/dv: None or empty = allocate
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                  at::Tensor dout, at::Tensor lse, double scale, long mod,
-                                 long modarg, at::Tensor slopes);
+                                 long modarg, at::Tensor slopes,
+                                 OptTensor dq, OptTensor dk, OptTensor dv);
 std::vector<at::Tensor> attn_bwd_split(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                        at::Tensor dout, at::Tensor lse, double scale, long mod,
                                        long modarg, at::Tensor slopes);
-std::vector<at::Tensor> attn_bwd_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
-                                     at::Tensor dout, at::Tensor lse, double scale, long mod,
-                                     long modarg, at::Tensor slopes,
-                                     at::Tensor dq, at::Tensor dk, at::Tensor dv);
 std::vector<at::Tensor> attn_bwd_blockmask(at::Tensor q, at::Tensor k, at::Tensor v,
                                            at::Tensor o, at::Tensor dout, at::Tensor lse,
                                            double scale, at::Tensor gran, at::Tensor bits,
@@ -73,11 +71,8 @@ std::vector<at::Tensor> attn_fwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, d
                                      at::Tensor doc_start);
 std::vector<at::Tensor> attn_bwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                      at::Tensor dout, at::Tensor lse, double scale,
-                                     at::Tensor doc_start, at::Tensor doc_end);
-std::vector<at::Tensor> attn_bwd_doc_out(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
-                                         at::Tensor dout, at::Tensor lse, double scale,
-                                         at::Tensor doc_start, at::Tensor doc_end,
-                                         at::Tensor dq, at::Tensor dk, at::Tensor dv);
+                                     at::Tensor doc_start, at::Tensor doc_end,
+                                     OptTensor dq, OptTensor dk, OptTensor dv);
 // sampling.hip
 at::Tensor sample_token(at::Tensor logits, double temperature, double top_p, double min_p,
                         long seed);
@@ -108,6 +103,7 @@ at::Tensor afrag_transform_test(at::Tensor M);
 at::Tensor tr16_frag_test(at::Tensor X);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  using namespace pybind11::literals;
   m.def("rmsnorm_fwd", &rmsnorm_fwd, "RMSNorm forward (y, rstd)");
   m.def("rmsnorm_bwd", &rmsnorm_bwd, "RMSNorm backward (dx, dw)");
   m.def("rmsnorm_fwd_res", &rmsnorm_fwd_res, "fused residual-add + RMSNorm fwd (y, rstd[, s][, amax])");
@@ -139,18 +135,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd, "flash attention forward (o, lse)");
   m.def("attn_fwd_blockmask", &attn_fwd_blockmask,
         "flash attention fwd with device block-mask/bits/bias (K2 flex)");
-  m.def("attn_bwd", &attn_bwd, "flash attention backward (dq, dk, dv)");
+  m.def("attn_bwd", &attn_bwd,
+        "flash attention backward (dq, dk, dv); dq/dk/dv given: strided out views (fused dQKV)",
+        "q"_a, "k"_a, "v"_a, "o"_a, "dout"_a, "lse"_a, "scale"_a, "mod"_a, "modarg"_a, "slopes"_a,
+        "dq"_a = py::none(), "dk"_a = py::none(), "dv"_a = py::none());
   m.def("attn_bwd_split", &attn_bwd_split,
         "attn_bwd on the split dK / dV kernels (reference for the merged dK+dV kernel)");
-  m.def("attn_bwd_out", &attn_bwd_out,
-        "flash attention backward into strided out views (fused dQKV)");
   m.def("attn_bwd_blockmask", &attn_bwd_blockmask,
         "backward of attn_fwd_blockmask (dq, dk, dv); bias gets no gradient");
   m.def("attn_fwd_doc", &attn_fwd_doc,
         "flash attention forward with a packed-sequence document mask (o, lse)");
-  m.def("attn_bwd_doc", &attn_bwd_doc, "backward of attn_fwd_doc (dq, dk, dv)");
-  m.def("attn_bwd_doc_out", &attn_bwd_doc_out,
-        "backward of attn_fwd_doc into strided out views (fused dQKV)");
+  m.def("attn_bwd_doc", &attn_bwd_doc,
+        "backward of attn_fwd_doc (dq, dk, dv); dq/dk/dv as in attn_bwd",
+        "q"_a, "k"_a, "v"_a, "o"_a, "dout"_a, "lse"_a, "scale"_a, "doc_start"_a, "doc_end"_a,
+        "dq"_a = py::none(), "dk"_a = py::none(), "dv"_a = py::none());
   m.def("sample_token", &sample_token, "fused temperature/min-p sampling");
   m.def("sample_token_dev", &sample_token_dev,
         "graph-capturable sampling (device position salt)");

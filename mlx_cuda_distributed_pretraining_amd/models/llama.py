@@ -178,6 +178,20 @@ class Attention(nn.Module):
                                 self.args.rms_norm_eps, trad, offset)
         return apply_rope(q, cos, sin, trad, offset), apply_rope(k, cos, sin, trad, offset)
 
+    def _split_qkv(self, qkv: torch.Tensor):
+        """Fused projection output -> q, k, v as [B, S, H, D] views."""
+        B, S, _ = qkv.shape
+        Hq, Hkv, D = self.n_heads, self.n_kv_heads, self.head_dim
+        q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+        return q.view(B, S, Hq, D), k.view(B, S, Hkv, D), v.view(B, S, Hkv, D)
+
+    def _project_out(self, o: torch.Tensor) -> torch.Tensor:
+        """wo, then back to the S-sharded (SP training) / replicated (TP) stream."""
+        out = self.wo(o.reshape(o.shape[0], o.shape[1], -1))
+        if getattr(self, "_sp", False) and self.training:
+            return scatter_sp(out)
+        return reduce_from_tp(out) if getattr(self, "_tp", False) else out
+
     def forward(self, x: torch.Tensor, cache: Optional[KVCache] = None,
                 doc_start: Optional[torch.Tensor] = None,
                 doc_end: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -210,26 +224,14 @@ class Attention(nn.Module):
             # custom mask (Model.set_flex_mask): unfused qkv split + RoPE,
             # then flex_attention — on bf16 GPU inputs that is the
             # MOD_BLOCKMASK kernels forward and backward
-            q, k, v = qkv.split(
-                [
-                    self.n_heads * self.head_dim,
-                    self.n_kv_heads * self.head_dim,
-                    self.n_kv_heads * self.head_dim,
-                ],
-                dim=-1,
-            )
+            q, k, v = self._split_qkv(qkv)
             cos, sin = self.rope_table.get(S, x.device, 0)
-            q, k = self._rope(q.view(B, S, self.n_heads, self.head_dim),
-                              k.view(B, S, self.n_kv_heads, self.head_dim), cos, sin, 0)
-            v = v.view(B, S, self.n_kv_heads, self.head_dim)
+            q, k = self._rope(q, k, cos, sin, 0)
             if isinstance(self.flex_mask, CompiledBlockMask):
                 o = flex_attention(q, k, v, block_mask=self.flex_mask, scale=self.scale)
             else:
                 o = flex_attention(q, k, v, mask_mod=self.flex_mask, scale=self.scale)
-            out = self.wo(o.reshape(B, S, -1))
-            if getattr(self, "_sp", False) and self.training:
-                return scatter_sp(out)
-            return reduce_from_tp(out) if getattr(self, "_tp", False) else out
+            return self._project_out(o)
         if cache is None and atype != "simple":
             # training fast path: one fused autograd node over the fused QKV
             # tensor (RoPE + attention; backward writes dQKV in place — no
@@ -247,23 +249,9 @@ class Attention(nn.Module):
                 k_norm_weight=self.k_norm.weight if self.args.qk_norm else None,
                 norm_eps=self.args.rms_norm_eps,
             )
-            out = self.wo(o.reshape(B, S, -1))
-            if getattr(self, "_sp", False) and self.training:
-                return scatter_sp(out)
-            return reduce_from_tp(out) if getattr(self, "_tp", False) else out
+            return self._project_out(o)
 
-        q, k, v = qkv.split(
-            [
-                self.n_heads * self.head_dim,
-                self.n_kv_heads * self.head_dim,
-                self.n_kv_heads * self.head_dim,
-            ],
-            dim=-1,
-        )
-        q = q.view(B, S, self.n_heads, self.head_dim)
-        k = k.view(B, S, self.n_kv_heads, self.head_dim)
-        v = v.view(B, S, self.n_kv_heads, self.head_dim)
-
+        q, k, v = self._split_qkv(qkv)
         offset = cache.offset if cache is not None else 0
         cos, sin = self.rope_table.get(S, x.device, offset)
         q, k = self._rope(q, k, cos, sin, offset)
@@ -284,10 +272,7 @@ class Attention(nn.Module):
                 prefix_len=self.args.attention_prefix_len if atype == "flex" else None,
                 alibi_slopes=self.alibi_slopes if self.args.use_alibi else None,
             )
-        out = self.wo(o.reshape(B, S, -1))
-        if getattr(self, "_sp", False) and self.training:
-            return scatter_sp(out)
-        return reduce_from_tp(out) if getattr(self, "_tp", False) else out
+        return self._project_out(o)
 
 
 class MLP(nn.Module):

@@ -16,7 +16,7 @@ zero transpose copies on the hot path.)
 from __future__ import annotations
 
 import math
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -166,138 +166,125 @@ def document_bounds(tokens: torch.Tensor, bos_id: Optional[int] = None,
     return start.to(torch.int32).contiguous(), _doc_end_from_starts(is_start)
 
 
-def _doc_pair(doc_start, doc_end, B: int, S: int, device):
-    """Normalise the document tensors for the kernels: int32, contiguous,
-    [B, S], on ``device``; doc_end derived from doc_start when omitted (column
-    s opens a document exactly when doc_start[b, s] == s)."""
-    if tuple(doc_start.shape) != (B, S):
-        raise ValueError(f"doc_start must be [B, S] = [{B}, {S}], got {tuple(doc_start.shape)}")
-    doc_start = doc_start.to(device=device, dtype=torch.int32).contiguous()
-    if doc_end is None:
-        idx = torch.arange(S, device=device, dtype=torch.int32)
-        doc_end = _doc_end_from_starts(doc_start == idx)
-    else:
-        if tuple(doc_end.shape) != (B, S):
-            raise ValueError(f"doc_end must be [B, S] = [{B}, {S}], got {tuple(doc_end.shape)}")
-        doc_end = doc_end.to(device=device, dtype=torch.int32).contiguous()
-    return doc_start, doc_end
+class _Mask(NamedTuple):
+    """The mask of one flash-attention call, in the form the kernels and the
+    reference take it. ``build`` is the one place that checks and normalises
+    the public keywords; ``fwd`` / ``bwd`` are the one place that picks the
+    mod-code or the document binding."""
 
+    causal: bool
+    window: Optional[int]
+    prefix_len: Optional[int]
+    slopes: torch.Tensor  # f32 ALiBi slopes [Hq]; empty = no ALiBi
+    doc_start: Optional[torch.Tensor]  # int32 contiguous [B, S], or None
+    doc_end: Optional[torch.Tensor]  # likewise; set whenever doc_start is
 
-def _check_doc_args(doc_start, doc_end, causal, window, prefix_len, alibi_slopes, Sq, Skv):
-    if doc_start is None:
-        if doc_end is not None:
-            raise ValueError("doc_end needs doc_start")
-        return
-    if window is not None or prefix_len is not None or alibi_slopes is not None:
-        raise ValueError("document mask (doc_start) cannot be combined with "
-                         "window, prefix_len or ALiBi")
-    if not causal:
-        raise ValueError("document mask (doc_start) is causal: causal=False is not supported")
-    if Sq != Skv:
-        raise ValueError(f"document mask (doc_start) is training-only: Sq ({Sq}) != Skv ({Skv})")
+    @classmethod
+    def build(cls, causal, window, prefix_len, alibi_slopes, doc_start, doc_end,
+              B: int, Sq: int, Skv: int, Hq: int, device) -> "_Mask":
+        if alibi_slopes is not None and not isinstance(alibi_slopes, torch.Tensor):
+            # an int head count builds the standard 2^(-8(i+1)/H) slopes —
+            # matches the reference's loose API
+            alibi_slopes = torch.tensor([2 ** (-8.0 * (i + 1) / Hq) for i in range(Hq)],
+                                        dtype=torch.float32, device=device)
+        if doc_start is None:
+            if doc_end is not None:
+                raise ValueError("doc_end needs doc_start")
+        else:
+            if window is not None or prefix_len is not None or alibi_slopes is not None:
+                raise ValueError("document mask (doc_start) cannot be combined with "
+                                 "window, prefix_len or ALiBi")
+            if not causal:
+                raise ValueError("document mask (doc_start) is causal: causal=False is not "
+                                 "supported")
+            if Sq != Skv:
+                raise ValueError(f"document mask (doc_start) is training-only: Sq ({Sq}) != "
+                                 f"Skv ({Skv})")
+            # int32, contiguous, [B, S], on ``device``; doc_end derived from
+            # doc_start when omitted (column s opens a document exactly when
+            # doc_start[b, s] == s)
+            for name, t in (("doc_start", doc_start), ("doc_end", doc_end)):
+                if t is not None and tuple(t.shape) != (B, Sq):
+                    raise ValueError(f"{name} must be [B, S] = [{B}, {Sq}], got {tuple(t.shape)}")
+            doc_start = doc_start.to(device=device, dtype=torch.int32).contiguous()
+            if doc_end is None:
+                idx = torch.arange(Sq, device=device, dtype=torch.int32)
+                doc_end = _doc_end_from_starts(doc_start == idx)
+            else:
+                doc_end = doc_end.to(device=device, dtype=torch.int32).contiguous()
+        slopes = (alibi_slopes.float().contiguous() if alibi_slopes is not None
+                  else torch.empty(0, dtype=torch.float32, device=device))
+        return cls(causal, window, prefix_len, slopes, doc_start, doc_end)
+
+    @property
+    def mod(self) -> int:
+        return _mods_to_code(self.causal, self.window, self.prefix_len, self.slopes.numel() > 0)
+
+    @property
+    def modarg(self) -> int:
+        return int(self.window if self.window is not None
+                   else (self.prefix_len if self.prefix_len is not None else 0))
+
+    def save(self, ctx, *tensors):
+        """ctx.save_for_backward of a node's own tensors followed by the
+        mask's; ``load`` undoes it."""
+        ctx.save_for_backward(*tensors, *self[3:])
+        ctx.mask_meta = self[:3]
+
+    @classmethod
+    def load(cls, ctx):
+        *tensors, slopes, doc_start, doc_end = ctx.saved_tensors
+        return cls(*ctx.mask_meta, slopes, doc_start, doc_end), tensors
+
+    def ref(self, q, k, v, scale, return_lse=False):
+        return attention_ref(q, k, v, causal=self.causal, scale=scale, window=self.window,
+                             prefix_len=self.prefix_len,
+                             alibi_slopes=self.slopes if self.slopes.numel() else None,
+                             return_lse=return_lse, doc_start=self.doc_start)
+
+    def fwd(self, ext, q, k, v, scale):
+        if self.doc_start is not None:
+            return ext.attn_fwd_doc(q, k, v, scale, self.doc_start)
+        return ext.attn_fwd(q, k, v, scale, self.mod, self.modarg, self.slopes)
+
+    def bwd(self, ext, q, k, v, o, do, lse, scale, dq=None, dk=None, dv=None):
+        """dq/dk/dv: out views to write in place; None or empty = allocate."""
+        if self.doc_start is not None:
+            return ext.attn_bwd_doc(q, k, v, o, do, lse, scale, self.doc_start, self.doc_end,
+                                    dq, dk, dv)
+        return ext.attn_bwd(q, k, v, o, do, lse, scale, self.mod, self.modarg, self.slopes,
+                            dq, dk, dv)
 
 
 class _FlashAttnFn(torch.autograd.Function):
+    """Kernels on bf16 GPU inputs, the fp32 composition otherwise (mask checks:
+    _Mask.build)."""
+
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, window, prefix_len, alibi_slopes,
-                doc_start=None, doc_end=None):
+    def forward(ctx, q, k, v, scale, mask):
         scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-        if doc_start is not None:
-            # document mask: attn_fwd_doc / attn_bwd_doc on the kernel path,
-            # the fp32 composition otherwise (argument checks: flash_attention)
-            hip = use_hip(q, k, v, dtypes=(torch.bfloat16,))
-            if hip:
-                o, lse = get_ext().attn_fwd_doc(q, k, v, scale, doc_start)
-            else:
-                o, lse = attention_ref(q, k, v, causal=True, scale=scale,
-                                       return_lse=True, doc_start=doc_start)
-            ctx.save_for_backward(q, k, v, o, lse, doc_start, doc_end)
-            ctx.meta = (scale, hip)
-            ctx.doc = True
-            return o
-        ctx.doc = False
-        if use_hip(q, k, v, dtypes=(torch.bfloat16,)):
-            ext = get_ext()
-            mod = _mods_to_code(causal, window, prefix_len, alibi_slopes is not None)
-            modarg = int(
-                window
-                if window is not None
-                else (prefix_len if prefix_len is not None else 0)
-            )
-            slopes = (
-                alibi_slopes.float().contiguous()
-                if alibi_slopes is not None
-                else torch.empty(0, dtype=torch.float32, device=q.device)
-            )
-            o, lse = ext.attn_fwd(q, k, v, scale, mod, modarg, slopes)
-            ctx.save_for_backward(q, k, v, o, lse, slopes)
-            ctx.meta = (causal, scale, window, prefix_len, True)
-            return o
-        o, lse = attention_ref(
-            q, k, v, causal=causal, scale=scale, window=window,
-            prefix_len=prefix_len, alibi_slopes=alibi_slopes, return_lse=True,
-        )
-        slopes = (
-            alibi_slopes.float().contiguous()
-            if alibi_slopes is not None
-            else torch.empty(0, dtype=torch.float32)
-        )
-        ctx.save_for_backward(q, k, v, o, lse, slopes)
-        ctx.meta = (causal, scale, window, prefix_len, False)
+        hip = use_hip(q, k, v, dtypes=(torch.bfloat16,))
+        if hip:
+            o, lse = mask.fwd(get_ext(), q, k, v, scale)
+        else:
+            o, lse = mask.ref(q, k, v, scale, return_lse=True)
+        mask.save(ctx, q, k, v, o, lse)
+        ctx.meta = (scale, hip)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        if ctx.doc:
-            q, k, v, o, lse, doc_start, doc_end = ctx.saved_tensors
-            scale, hip = ctx.meta
-            if hip:
-                dq, dk, dv = get_ext().attn_bwd_doc(q, k, v, o, do, lse, scale,
-                                                    doc_start, doc_end)
-                return (dq, dk, dv) + (None,) * 7
-            with torch.enable_grad():
-                qf = q.detach().float().requires_grad_(True)
-                kf = k.detach().float().requires_grad_(True)
-                vf = v.detach().float().requires_grad_(True)
-                of = attention_ref(qf, kf, vf, causal=True, scale=scale, doc_start=doc_start)
-                grads = torch.autograd.grad(of, [qf, kf, vf], do.float())
-            return (grads[0].to(q.dtype), grads[1].to(k.dtype), grads[2].to(v.dtype)) + (None,) * 7
-        q, k, v, o, lse, slopes = ctx.saved_tensors
-        causal, scale, window, prefix_len, hip = ctx.meta
+        mask, (q, k, v, o, lse) = _Mask.load(ctx)
+        scale, hip = ctx.meta
         if hip:
-            ext = get_ext()
-            mod = _mods_to_code(causal, window, prefix_len, slopes.numel() > 0)
-            modarg = int(
-                window if window is not None else (prefix_len if prefix_len is not None else 0)
-            )
-            dq, dk, dv = ext.attn_bwd(q, k, v, o, do, lse, scale, mod, modarg, slopes)
-            return (dq, dk, dv) + (None,) * 7
+            return (*mask.bwd(get_ext(), q, k, v, o, do, lse, scale), None, None)
         # CPU reference backward: recompute with autograd in fp32
         with torch.enable_grad():
             qf = q.detach().float().requires_grad_(True)
             kf = k.detach().float().requires_grad_(True)
             vf = v.detach().float().requires_grad_(True)
-            alibi = slopes if slopes.numel() > 0 else None
-            of = attention_ref(
-                qf, kf, vf, causal=causal, scale=scale, window=window,
-                prefix_len=prefix_len, alibi_slopes=alibi,
-            )
-            grads = torch.autograd.grad(of, [qf, kf, vf], do.float())
-        return (
-            grads[0].to(q.dtype), grads[1].to(k.dtype), grads[2].to(v.dtype),
-            None, None, None, None, None, None, None,
-        )
-
-
-
-def _norm_alibi(alibi_slopes, num_heads: int, device) -> "Optional[torch.Tensor]":
-    """Accept either a per-head slope tensor or an int head count (builds the
-    standard 2^(-8(i+1)/H) slopes) — matches the reference's loose API."""
-    if alibi_slopes is None or isinstance(alibi_slopes, torch.Tensor):
-        return alibi_slopes
-    h = int(num_heads)
-    return torch.tensor([2 ** (-8.0 * (i + 1) / h) for i in range(h)],
-                        dtype=torch.float32, device=device)
+            grads = torch.autograd.grad(mask.ref(qf, kf, vf, scale), [qf, kf, vf], do.float())
+        return grads[0].to(q.dtype), grads[1].to(k.dtype), grads[2].to(v.dtype), None, None
 
 
 def flash_attention(
@@ -313,7 +300,7 @@ def flash_attention(
     doc_end: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Tiled attention, BSHD layout: [B,S,Hq,D] x [B,S,Hkv,D] -> [B,S,Hq,D]
-    (q.shape[2] is the HEAD count — _norm_alibi relies on that).
+    (q.shape[2] is the HEAD count — an int ``alibi_slopes`` relies on that).
 
     Document mask (packed sequences)
     --------------------------------
@@ -337,27 +324,23 @@ def flash_attention(
       * RoPE needs no per-document position reset: scores depend on
         q_pos - k_pos only.
     """
-    alibi_slopes = _norm_alibi(alibi_slopes, q.shape[2], q.device)
-    _check_doc_args(doc_start, doc_end, causal, window, prefix_len, alibi_slopes,
-                    q.shape[1], k.shape[1])
-    if doc_start is not None:
-        doc_start, doc_end = _doc_pair(doc_start, doc_end, q.shape[0], q.shape[1], q.device)
-        return _FlashAttnFn.apply(q, k, v, True, scale, None, None, None, doc_start, doc_end)
-    return _FlashAttnFn.apply(q, k, v, causal, scale, window, prefix_len, alibi_slopes)
+    B, Sq, Hq, _ = q.shape
+    mask = _Mask.build(causal, window, prefix_len, alibi_slopes, doc_start, doc_end,
+                       B, Sq, k.shape[1], Hq, q.device)
+    return _FlashAttnFn.apply(q, k, v, scale, mask)
 
 
 class _RopeAttnQKVFn(torch.autograd.Function):
     """Fused qkv-slice -> RoPE(q,k) -> flash attention, HIP path only.
 
     Takes the FUSED [B, S, (Hq+2*Hkv)*D] projection output directly so the
-    backward can write dQ/dK/dV straight into ONE dqkv buffer (attn_bwd_out /
-    rope_fwd_out strided-out variants) — eliminating autograd's
+    backward can write dQ/dK/dV straight into ONE dqkv buffer (strided out
+    views for attn_bwd / rope_fwd_out) — eliminating autograd's
     split-backward torch.cat over the three grads (a full extra read+write
     of the qkv-grad per layer, the CatArrayBatchedCopy kernel in profiles)."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, Hq, Hkv, D, traditional, causal, scale,
-                window, prefix_len, alibi_slopes, doc_start=None, doc_end=None):
+    def forward(ctx, qkv, cos, sin, Hq, Hkv, D, traditional, scale, mask):
         B, S, _ = qkv.shape
         scale = scale if scale is not None else 1.0 / math.sqrt(D)
         q = qkv[..., : Hq * D].view(B, S, Hq, D)
@@ -366,26 +349,15 @@ class _RopeAttnQKVFn(torch.autograd.Function):
         ext = get_ext()
         qr = ext.rope_fwd(q, cos, sin, traditional, 0, False)
         kr = ext.rope_fwd(k, cos, sin, traditional, 0, False)
-        mod = _mods_to_code(causal, window, prefix_len, alibi_slopes is not None)
-        modarg = int(window if window is not None
-                     else (prefix_len if prefix_len is not None else 0))
-        slopes = (alibi_slopes.float().contiguous() if alibi_slopes is not None
-                  else torch.empty(0, dtype=torch.float32, device=qkv.device))
-        ctx.doc = doc_start is not None
-        if ctx.doc:
-            # document mask (argument checks: rope_flash_attention_qkv)
-            o, lse = ext.attn_fwd_doc(qr, kr, v, scale, doc_start)
-            ctx.save_for_backward(qkv, qr, kr, o, lse, cos, sin, slopes, doc_start, doc_end)
-        else:
-            o, lse = ext.attn_fwd(qr, kr, v, scale, mod, modarg, slopes)
-            ctx.save_for_backward(qkv, qr, kr, o, lse, cos, sin, slopes)
-        ctx.meta = (Hq, Hkv, D, traditional, scale, mod, modarg)
+        o, lse = mask.fwd(ext, qr, kr, v, scale)
+        mask.save(ctx, qkv, qr, kr, o, lse, cos, sin)
+        ctx.meta = (Hq, Hkv, D, traditional, scale)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, qr, kr, o, lse, cos, sin, slopes = ctx.saved_tensors[:8]
-        Hq, Hkv, D, traditional, scale, mod, modarg = ctx.meta
+        mask, (qkv, qr, kr, o, lse, cos, sin) = _Mask.load(ctx)
+        Hq, Hkv, D, traditional, scale = ctx.meta
         B, S, _ = qkv.shape
         ext = get_ext()
         v = qkv[..., (Hq + Hkv) * D :].view(B, S, Hkv, D)
@@ -394,16 +366,10 @@ class _RopeAttnQKVFn(torch.autograd.Function):
         dk_t = dqkv[..., Hq * D : (Hq + Hkv) * D].view(B, S, Hkv, D)
         dv_t = dqkv[..., (Hq + Hkv) * D :].view(B, S, Hkv, D)
         none = torch.empty(0, dtype=qkv.dtype, device=qkv.device)
-        if ctx.doc:
-            doc_start, doc_end = ctx.saved_tensors[8:]
-            dq_r, dk_r, _ = ext.attn_bwd_doc_out(qr, kr, v, o, do, lse, scale, doc_start,
-                                                 doc_end, none, none.clone(), dv_t)
-        else:
-            dq_r, dk_r, _ = ext.attn_bwd_out(qr, kr, v, o, do, lse, scale, mod,
-                                             modarg, slopes, none, none.clone(), dv_t)
+        dq_r, dk_r, _ = mask.bwd(ext, qr, kr, v, o, do, lse, scale, none, none.clone(), dv_t)
         ext.rope_fwd_out(dq_r, cos, sin, traditional, 0, True, dq_t)
         ext.rope_fwd_out(dk_r, cos, sin, traditional, 0, True, dk_t)
-        return (dqkv,) + (None,) * 13
+        return (dqkv,) + (None,) * 8
 
 
 class _QKNormRopeAttnQKVFn(torch.autograd.Function):
@@ -419,8 +385,7 @@ class _QKNormRopeAttnQKVFn(torch.autograd.Function):
     writes the dq|dk slices of dqkv and returns both weight gradients."""
 
     @staticmethod
-    def forward(ctx, qkv, q_w, k_w, cos, sin, Hq, Hkv, D, eps, traditional, causal, scale,
-                window, prefix_len, alibi_slopes, doc_start=None, doc_end=None):
+    def forward(ctx, qkv, q_w, k_w, cos, sin, Hq, Hkv, D, eps, traditional, scale, mask):
         B, S, _ = qkv.shape
         scale = scale if scale is not None else 1.0 / math.sqrt(D)
         x = qkv[..., : (Hq + Hkv) * D].view(B, S, Hq + Hkv, D)
@@ -432,26 +397,15 @@ class _QKNormRopeAttnQKVFn(torch.autograd.Function):
         wk = kernel_weight(k_w, qkv.dtype)
         y, rstd = ext.qknorm_rope_fwd(x, Hq, wq, wk, cos, sin, traditional, 0, eps)
         qr, kr = y[:, :, :Hq], y[:, :, Hq:]
-        mod = _mods_to_code(causal, window, prefix_len, alibi_slopes is not None)
-        modarg = int(window if window is not None
-                     else (prefix_len if prefix_len is not None else 0))
-        slopes = (alibi_slopes.float().contiguous() if alibi_slopes is not None
-                  else torch.empty(0, dtype=torch.float32, device=qkv.device))
-        ctx.doc = doc_start is not None
-        if ctx.doc:
-            o, lse = ext.attn_fwd_doc(qr, kr, v, scale, doc_start)
-            ctx.save_for_backward(qkv, y, rstd, wq, wk, o, lse, cos, sin, slopes,
-                                  doc_start, doc_end)
-        else:
-            o, lse = ext.attn_fwd(qr, kr, v, scale, mod, modarg, slopes)
-            ctx.save_for_backward(qkv, y, rstd, wq, wk, o, lse, cos, sin, slopes)
-        ctx.meta = (Hq, Hkv, D, traditional, scale, mod, modarg, q_w.dtype, k_w.dtype)
+        o, lse = mask.fwd(ext, qr, kr, v, scale)
+        mask.save(ctx, qkv, y, rstd, wq, wk, o, lse, cos, sin)
+        ctx.meta = (Hq, Hkv, D, traditional, scale, q_w.dtype, k_w.dtype)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, y, rstd, wq, wk, o, lse, cos, sin, slopes = ctx.saved_tensors[:10]
-        Hq, Hkv, D, traditional, scale, mod, modarg, qw_dtype, kw_dtype = ctx.meta
+        mask, (qkv, y, rstd, wq, wk, o, lse, cos, sin) = _Mask.load(ctx)
+        Hq, Hkv, D, traditional, scale, qw_dtype, kw_dtype = ctx.meta
         B, S, _ = qkv.shape
         ext = get_ext()
         x = qkv[..., : (Hq + Hkv) * D].view(B, S, Hq + Hkv, D)
@@ -462,15 +416,9 @@ class _QKNormRopeAttnQKVFn(torch.autograd.Function):
         dv_t = dqkv[..., (Hq + Hkv) * D :].view(B, S, Hkv, D)
         g_r = torch.empty_like(y)  # rotated dq | dk
         dq_r, dk_r = g_r[:, :, :Hq], g_r[:, :, Hq:]
-        if ctx.doc:
-            doc_start, doc_end = ctx.saved_tensors[10:]
-            ext.attn_bwd_doc_out(qr, kr, v, o, do, lse, scale, doc_start, doc_end,
-                                 dq_r, dk_r, dv_t)
-        else:
-            ext.attn_bwd_out(qr, kr, v, o, do, lse, scale, mod, modarg, slopes,
-                             dq_r, dk_r, dv_t)
+        mask.bwd(ext, qr, kr, v, o, do, lse, scale, dq_r, dk_r, dv_t)
         dw = ext.qknorm_rope_bwd(g_r, x, rstd, Hq, wq, wk, cos, sin, traditional, 0, dqk_t)
-        return (dqkv, dw[0].to(qw_dtype), dw[1].to(kw_dtype)) + (None,) * 14
+        return (dqkv, dw[0].to(qw_dtype), dw[1].to(kw_dtype)) + (None,) * 9
 
 
 def rope_flash_attention_qkv(
@@ -501,44 +449,31 @@ def rope_flash_attention_qkv(
     ``q_norm_weight`` / ``k_norm_weight`` (``[head_dim]``, both or neither):
     per-head QK-norm before RoPE, see ``ops.qk_norm``. With both ``None`` the
     path is the plain RoPE + attention one."""
-    B, S, _ = qkv.shape
-    _check_doc_args(doc_start, doc_end, causal, window, prefix_len, alibi_slopes, S, S)
-    if (q_norm_weight is None) != (k_norm_weight is None):
-        raise ValueError("QK-norm needs both q_norm_weight and k_norm_weight")
-    if q_norm_weight is not None:
-        from .qk_norm import HIP_HEAD_DIMS, qk_norm_rope
-
-        Hq, Hkv, D = n_heads, n_kv_heads, head_dim
-        if D in HIP_HEAD_DIMS and use_hip(qkv, dtypes=(torch.bfloat16,)):
-            if doc_start is not None:
-                doc_start, doc_end = _doc_pair(doc_start, doc_end, B, S, qkv.device)
-            return _QKNormRopeAttnQKVFn.apply(
-                qkv, q_norm_weight, k_norm_weight, cos, sin, Hq, Hkv, D, float(norm_eps),
-                traditional, causal, scale, window, prefix_len, alibi_slopes,
-                doc_start, doc_end)
-        q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
-        q, k = qk_norm_rope(q.view(B, S, Hq, D), k.view(B, S, Hkv, D), q_norm_weight,
-                            k_norm_weight, cos, sin, norm_eps, traditional, 0)
-        return flash_attention(q, k, v.view(B, S, Hkv, D), causal=causal, scale=scale,
-                               window=window, prefix_len=prefix_len,
-                               alibi_slopes=alibi_slopes, doc_start=doc_start,
-                               doc_end=doc_end)
-    if use_hip(qkv, dtypes=(torch.bfloat16,)):
-        if doc_start is not None:
-            doc_start, doc_end = _doc_pair(doc_start, doc_end, B, S, qkv.device)
-        return _RopeAttnQKVFn.apply(qkv, cos, sin, n_heads, n_kv_heads, head_dim,
-                                    traditional, causal, scale, window,
-                                    prefix_len, alibi_slopes, doc_start, doc_end)
+    from .qk_norm import HIP_HEAD_DIMS, qk_norm_rope
     from .rope import apply_rope
 
+    B, S, _ = qkv.shape
     Hq, Hkv, D = n_heads, n_kv_heads, head_dim
+    mask = _Mask.build(causal, window, prefix_len, alibi_slopes, doc_start, doc_end,
+                       B, S, S, Hq, qkv.device)
+    if (q_norm_weight is None) != (k_norm_weight is None):
+        raise ValueError("QK-norm needs both q_norm_weight and k_norm_weight")
+    qk_norm = q_norm_weight is not None
+    if (not qk_norm or D in HIP_HEAD_DIMS) and use_hip(qkv, dtypes=(torch.bfloat16,)):
+        if qk_norm:
+            return _QKNormRopeAttnQKVFn.apply(
+                qkv, q_norm_weight, k_norm_weight, cos, sin, Hq, Hkv, D, float(norm_eps),
+                traditional, scale, mask)
+        return _RopeAttnQKVFn.apply(qkv, cos, sin, Hq, Hkv, D, traditional, scale, mask)
     q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
-    q = apply_rope(q.view(B, S, Hq, D), cos, sin, traditional, 0)
-    k = apply_rope(k.view(B, S, Hkv, D), cos, sin, traditional, 0)
-    return flash_attention(q, k, v.view(B, S, Hkv, D), causal=causal, scale=scale,
-                           window=window, prefix_len=prefix_len,
-                           alibi_slopes=alibi_slopes, doc_start=doc_start,
-                           doc_end=doc_end)
+    q, k = q.view(B, S, Hq, D), k.view(B, S, Hkv, D)
+    if qk_norm:
+        q, k = qk_norm_rope(q, k, q_norm_weight, k_norm_weight, cos, sin, norm_eps,
+                            traditional, 0)
+    else:
+        q = apply_rope(q, cos, sin, traditional, 0)
+        k = apply_rope(k, cos, sin, traditional, 0)
+    return _FlashAttnFn.apply(q, k, v.view(B, S, Hkv, D), scale, mask)
 
 
 def flex_attention(
@@ -693,6 +628,16 @@ class BlockMask:
         self.block_size = block_size
 
 
+def _live_span(live: torch.Tensor) -> torch.Tensor:
+    """bool [..., n] -> int32 [..., 2]: first / last+1 True index along the last
+    dim, [0, 0] where there is none. Tensor ops only, no host sync."""
+    n = live.shape[-1]
+    idx = torch.arange(n, device=live.device)
+    last = torch.where(live, idx + 1, 0).amax(-1)
+    first = torch.where(live, idx, n).amin(-1) * (last > 0)
+    return torch.stack([first, last], dim=-1).to(torch.int32)
+
+
 class CompiledBlockMask:
     """An arbitrary ``mask_mod`` compiled into device tensors that drive the
     K1 kernel's block-skip / per-element-bit machinery (VERDICT r1 #5;
@@ -720,58 +665,43 @@ class CompiledBlockMask:
                  device="cuda"):
         self.B, self.H, self.Q_LEN, self.KV_LEN = B, H, Q_LEN, KV_LEN
         self._mask_mod = mask_mod  # kept for the non-additive score_mod fallback
-        qi = torch.arange(Q_LEN, device=device)
-        ki = torch.arange(KV_LEN, device=device)
+        pad = torch.nn.functional.pad
+        idx = lambda n: torch.arange(n, device=device)
+        qi, ki = idx(Q_LEN), idx(KV_LEN)
         nq32 = (Q_LEN + 31) // 32
         nkv = (KV_LEN + self.KVB - 1) // self.KVB
         nqpb = (Q_LEN + self.QPB - 1) // self.QPB
+        nkpb = (KV_LEN + self.QPB - 1) // self.QPB  # the backward's kv blocks
         self.gran = torch.zeros(B, H, nq32, nkv, dtype=torch.uint8, device=device)
         self.bits = torch.zeros(B, H, Q_LEN, (KV_LEN + 7) // 8, dtype=torch.uint8,
                                 device=device)
-        self.range = torch.zeros(B, H, nqpb, 2, dtype=torch.int32, device=device)
-        nkpb = (KV_LEN + self.QPB - 1) // self.QPB  # the backward's kv blocks
-        self.qrange = torch.zeros(B, H, nkpb, 2, dtype=torch.int32, device=device)
         weights = (1 << torch.arange(8, device=device, dtype=torch.int32)).to(torch.uint8)
+        # IN-RANGE elements per granule (the last granule row / column is ragged)
+        in_range = ((Q_LEN - 32 * idx(nq32)).clamp(max=32).unsqueeze(1)
+                    * (KV_LEN - self.KVB * idx(nkv)).clamp(max=self.KVB))
         for b in range(B):
             for h in range(H):
                 keep = mask_mod(b, h, qi.unsqueeze(1), ki.unsqueeze(0))
-                keep = keep.to(torch.bool)  # [Q, KV], exact
-                kp = torch.zeros(Q_LEN, nkv * self.KVB // 8 * 8, dtype=torch.bool,
-                                 device=device)
-                kp[:, :KV_LEN] = keep
-                packed = (kp.reshape(Q_LEN, -1, 8).to(torch.uint8) *
+                keep = keep.to(torch.bool).expand(Q_LEN, KV_LEN)  # [Q, KV], exact
+                # zero-pad to whole 32-row / 64-col granules
+                kp = pad(keep, (0, nkv * self.KVB - KV_LEN, 0, nq32 * 32 - Q_LEN))
+                packed = (kp[:Q_LEN].reshape(Q_LEN, -1, 8).to(torch.uint8) *
                           weights).sum(-1).to(torch.uint8)
                 self.bits[b, h] = packed[:, : (KV_LEN + 7) // 8]
-                # granule codes: pad to 32-row / 64-col granules
-                gq = torch.zeros(nq32 * 32, nkv * self.KVB, dtype=torch.bool,
-                                 device=device)
-                gq[:Q_LEN, :KV_LEN] = keep
-                g = gq.reshape(nq32, 32, nkv, self.KVB)
-                any_live = g.any(dim=(1, 3))
-                # "full" additionally requires every IN-RANGE element live
-                gq2 = torch.ones(nq32 * 32, nkv * self.KVB, dtype=torch.bool,
-                                 device=device)
-                gq2[:Q_LEN, :KV_LEN] = keep
-                all_live = gq2.reshape(nq32, 32, nkv, self.KVB).all(dim=(1, 3))
-                self.gran[b, h] = any_live.to(torch.uint8) + (any_live & all_live).to(torch.uint8)
-                # per 256-row block: first/last live kv tile. Slice the
-                # 8 granule rows explicitly — a reshape(nqpb, -1) misassigns
-                # rows whenever ceil(Q/32) is not a multiple of 8 (caught by
-                # tests/test_attention_cpu.py::..._bruteforce at Q=300).
-                for qb in range(nqpb):
-                    rows = any_live[qb * 8:(qb + 1) * 8]
-                    live = rows.any(dim=0).nonzero().flatten()
-                    if live.numel():
-                        self.range[b, h, qb, 0] = int(live.min())
-                        self.range[b, h, qb, 1] = int(live.max()) + 1
-                # transpose of range for the dK/dV kernels: per 256-row kv
-                # block (4 granule columns), first/last+1 live 32-row q tile
-                for kb in range(nkpb):
-                    cols = any_live[:, kb * 4:(kb + 1) * 4]
-                    live = cols.any(dim=1).nonzero().flatten()
-                    if live.numel():
-                        self.qrange[b, h, kb, 0] = int(live.min())
-                        self.qrange[b, h, kb, 1] = int(live.max()) + 1
+                # granule codes; "full" requires every IN-RANGE element live
+                live = kp.reshape(nq32, 32, nkv, self.KVB).sum(dim=(1, 3))
+                self.gran[b, h] = (live > 0).to(torch.uint8) + (live == in_range).to(torch.uint8)
+        any_live = self.gran > 0
+        # per 256-row block: first/last live kv tile. Pad the granule rows to
+        # whole blocks of 8 first — a reshape(nqpb, -1) misassigns rows
+        # whenever ceil(Q/32) is not a multiple of 8 (caught by
+        # tests/test_attention_cpu.py::..._bruteforce at Q=300).
+        rows = pad(any_live, (0, 0, 0, nqpb * 8 - nq32)).reshape(B, H, nqpb, 8, nkv)
+        self.range = _live_span(rows.any(dim=3))
+        # transpose of range for the dK/dV kernels: per 256-row kv block
+        # (4 granule columns), first/last+1 live 32-row q tile
+        cols = pad(any_live, (0, nkpb * 4 - nkv)).reshape(B, H, nq32, nkpb, 4)
+        self.qrange = _live_span(cols.any(dim=4).transpose(2, 3))
 
 
 def create_block_mask(

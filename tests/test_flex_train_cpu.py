@@ -31,8 +31,18 @@ def _cdiv(a, b):
     return (a + b - 1) // b
 
 
-SHAPES = [(300, 300), (512, 200)]
-MODS = [doc_band, checker]
+def dead_blocks(b, h, qi, ki):
+    """q rows 256..511 and kv columns 256..511 dead: one whole 256-row q block
+    and one whole 256-row kv block without a live element ([0, 0] rows of range
+    and qrange); partial granules elsewhere."""
+    return ~((qi // 256 == 1) | (ki // 256 == 1)) & ((qi + ki) % 3 != 0)
+
+
+# (300, 300): ragged granule rows (ceil(Q/32) = 10, not a multiple of 8);
+# (257, 129): a one-row second q block and a ragged kv block (ceil(KV/64) = 3,
+# not a multiple of 4); (33, 520): more kv blocks than q blocks
+SHAPES = [(300, 300), (512, 200), (257, 129), (33, 520)]
+MODS = [doc_band, checker, dead_blocks]
 
 
 @pytest.mark.parametrize("Q,KV", SHAPES)

@@ -1,6 +1,6 @@
 """Merged dK+dV attention backward kernel (csrc/attn_bwd.hip) on a real MI355X.
 
-Part 1: the merged path (attn_bwd / attn_bwd_out, the default at D=128) against
+Part 1: the merged path (attn_bwd, the default at D=128) against
 the split dK and dV kernels (attn_bwd_split) on the same inputs — bit-identical,
 since both form p and dS by the same code and accumulate in the same order.
 Part 2: the merged results against the fp32 attention_ref backward, under the
@@ -51,7 +51,7 @@ def run_case(ext, name):
     computed once and shared by the tests (nothing below modifies them)."""
     if name in _runs:
         return _runs[name]
-    from mlx_cuda_distributed_pretraining_amd.ops.attention import _mods_to_code, attention_ref
+    from mlx_cuda_distributed_pretraining_amd.ops.attention import _Mask, attention_ref
 
     B, S, Hq, Hkv, kw = CASES[name]
     torch.manual_seed(0)
@@ -61,9 +61,8 @@ def run_case(ext, name):
     alibi = None
     if kw.get("alibi"):
         alibi = torch.tensor([2 ** (-(i + 1)) for i in range(Hq)], device=dev())
-    mod = _mods_to_code(causal, window, prefix_len, alibi is not None)
-    modarg = int(window if window is not None else (prefix_len if prefix_len is not None else 0))
-    slopes = alibi.float().contiguous() if alibi is not None else torch.empty(0, device=dev())
+    mask = _Mask.build(causal, window, prefix_len, alibi, None, None, B, S, S, Hq, dev())
+    mod, modarg, slopes = mask.mod, mask.modarg, mask.slopes
     scale = 1.0 / math.sqrt(D)
     o, lse = ext.attn_fwd(q, k, v, scale, mod, modarg, slopes)
     dy = torch.randn_like(o)
@@ -102,7 +101,7 @@ def test_merged_matches_fp32_reference(ext, name):
 
 
 def test_merged_out_views_of_fused_buffer(ext):
-    """attn_bwd_out writing dq, dk and dv as row-strided views of one fused
+    """attn_bwd writing dq, dk and dv as row-strided views of one fused
     [B, S, (Hq + 2 Hkv) D] buffer: same bits as the split path, and nothing
     outside the views' own columns is disturbed."""
     r = run_case(ext, "causal")
@@ -111,7 +110,7 @@ def test_merged_out_views_of_fused_buffer(ext):
     dq_t = dqkv[..., : Hq * D].view(B, S, Hq, D)
     dk_t = dqkv[..., Hq * D: (Hq + Hkv) * D].view(B, S, Hkv, D)
     dv_t = dqkv[..., (Hq + Hkv) * D:].view(B, S, Hkv, D)
-    out = ext.attn_bwd_out(*r["args"], dq_t, dk_t, dv_t)
+    out = ext.attn_bwd(*r["args"], dq_t, dk_t, dv_t)
     want = torch.cat([t.reshape(B, S, -1) for t in r["split"]], dim=-1)
     assert torch.equal(dqkv, want), (dqkv.float() - want.float()).abs().max().item()
     for got, view in zip(out, (dq_t, dk_t, dv_t)):

@@ -338,8 +338,8 @@ def test_host_checks_reject_bad_attention_args(ext):
         lambda: ext.attn_bwd(q, k.half(), v, o, dout, lse, scale, 1, 0, none),
         lambda: ext.attn_bwd(q, k, v, o, dout, lse.double(), scale, 1, 0, none),  # lse f64
         lambda: ext.attn_bwd(q, k, v, o, dout.half(), lse, scale, 1, 0, none),    # dout fp16
-        lambda: ext.attn_bwd_out(q, k, v, o, dout, lse, scale, 1, 0, none,        # dq view f32
-                                 torch.empty(B, S, H, D, device=dev()), empty, empty.clone()),
+        lambda: ext.attn_bwd(q, k, v, o, dout, lse, scale, 1, 0, none,            # dq view f32
+                             torch.empty(B, S, H, D, device=dev()), empty, empty.clone()),
         lambda: ext.attn_fwd(q, k, v, scale, 4, 0, bad_slopes),             # slopes f64
         lambda: ext.attn_bwd(q, k, v, o, dout, lse, scale, 4, 0, bad_slopes),
         lambda: ext.attn_fwd(q, k, v, scale, 17, 0, none),                  # unknown mod
@@ -358,7 +358,7 @@ def test_host_checks_reject_bad_attention_args(ext):
 
 def test_fused_qkv_rope_attention_matches_composition(ext):
     """Fused qkv->RoPE->attention autograd node vs the op composition
-    (incl. dQKV written in place by attn_bwd_out/rope_fwd_out)."""
+    (incl. dQKV written in place by attn_bwd/rope_fwd_out into out views)."""
     from mlx_cuda_distributed_pretraining_amd.ops.attention import (
         flash_attention, rope_flash_attention_qkv,
     )
@@ -386,6 +386,72 @@ def test_fused_qkv_rope_attention_matches_composition(ext):
     assert torch.allclose(got_o.float(), o2.detach().float(), atol=3e-2, rtol=3e-2)
     assert torch.allclose(got_g.float(), qkv2.grad.float(), atol=5e-2, rtol=5e-2), \
         (got_g.float() - qkv2.grad.float()).abs().max()
+
+
+def _fused_mask_cases():
+    kinds = ("window64", "prefix100", "alibi", "doc")
+    return ([(128, kind, qk_norm) for kind in kinds for qk_norm in (False, True)]
+            + [(64, "window64", False)])
+
+
+@pytest.mark.parametrize("D,kind,qk_norm", _fused_mask_cases())
+def test_fused_qkv_nodes_match_composition_for_every_mask_kind(ext, D, kind, qk_norm):
+    """Both fused qkv nodes (plain and QK-norm) vs the unfused composition
+    split -> (QK-norm +) RoPE -> flash_attention, for the mask kinds beyond
+    causal. S=328: two 256-row blocks, the second ragged; GQA group of 2; the
+    doc case has a document (70..259) ending just past the block boundary and
+    one (260..327) inside the second block."""
+    from mlx_cuda_distributed_pretraining_amd.ops.attention import (
+        flash_attention, rope_flash_attention_qkv,
+    )
+    from mlx_cuda_distributed_pretraining_amd.ops.qk_norm import qk_norm_rope
+    from mlx_cuda_distributed_pretraining_amd.ops.rope import RopeTable, apply_rope
+
+    B, S, Hq, Hkv = 2, 328, 4, 2
+    g = torch.Generator(device="cpu").manual_seed(5)
+    cos, sin = RopeTable(D, 10000.0).get(S, dev(), 0)
+    qkv = torch.randn(B, S, (Hq + 2 * Hkv) * D, generator=g).to(dev(), torch.bfloat16)
+    qkv.requires_grad_(True)
+    do = torch.randn(B, S, Hq, D, generator=g).to(dev(), torch.bfloat16)
+    doc_start = torch.zeros(B, S, dtype=torch.int32)
+    for lo in (0, 70, 260):
+        doc_start[:, lo:] = lo
+    kw = {
+        "window64": dict(window=64),
+        "prefix100": dict(prefix_len=100),
+        "alibi": dict(alibi_slopes=torch.tensor([2.0 ** (-(i + 1)) for i in range(Hq)],
+                                                device=dev())),
+        "doc": dict(doc_start=doc_start.to(dev())),
+    }[kind]
+    ws = [(0.5 + torch.rand(D, generator=g)).to(dev(), torch.bfloat16).requires_grad_(True)
+          for _ in range(2 if qk_norm else 0)]
+    norm_kw = dict(q_norm_weight=ws[0], k_norm_weight=ws[1], norm_eps=1e-5) if qk_norm else {}
+
+    o = rope_flash_attention_qkv(qkv, cos, sin, Hq, Hkv, D, **kw, **norm_kw)
+    want_node = "_QKNormRopeAttnQKVFnBackward" if qk_norm else "_RopeAttnQKVFnBackward"
+    assert type(o.grad_fn).__name__ == want_node
+    o.backward(do)
+
+    qkv2 = qkv.detach().clone().requires_grad_(True)
+    ws2 = [w.detach().clone().requires_grad_(True) for w in ws]
+    q, k, v = qkv2.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+    q, k = q.view(B, S, Hq, D), k.view(B, S, Hkv, D)
+    if qk_norm:
+        q, k = qk_norm_rope(q, k, ws2[0], ws2[1], cos, sin, 1e-5, False, 0)
+    else:
+        q, k = apply_rope(q, cos, sin, False, 0), apply_rope(k, cos, sin, False, 0)
+    o2 = flash_attention(q, k, v.view(B, S, Hkv, D), causal=True, **kw)
+    o2.backward(do)
+
+    assert bool(torch.isfinite(o).all()) and bool(torch.isfinite(qkv.grad).all())
+    assert torch.allclose(o.detach().float(), o2.detach().float(), atol=3e-2, rtol=3e-2)
+    assert torch.allclose(qkv.grad.float(), qkv2.grad.float(), atol=5e-2, rtol=5e-2), \
+        (qkv.grad.float() - qkv2.grad.float()).abs().max()
+    for name, w, w2 in zip(("dw_q", "dw_k"), ws, ws2):
+        # bound of tests/test_gpu_qk_norm.py for the weight gradients
+        err = (w.grad.float() - w2.grad.float()).abs().max().item()
+        bound = 0.05 * max(w2.grad.float().abs().max().item(), 1.0)
+        assert math.isfinite(err) and err < bound, f"{name} err {err} >= {bound}"
 
 
 def test_static_decode_gpu_matches_eager(ext):
