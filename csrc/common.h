@@ -110,4 +110,7 @@ __global__ void reduce_partials_kernel(const float* __restrict__ partials, int n
   if (threadIdx.x == 0) *out = acc;
 }
 
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
+// long, not int: the flat optimizer buffers of the unsharded 7B configs pass
+// 2^31 elements, and an int here made their grid negative.
+constexpr long cdiv(long a, long b) { return (a + b - 1) / b; }
+static_assert(cdiv(1L << 33, 256) == (1L << 25), "cdiv must not truncate to int");

@@ -5,6 +5,7 @@
 // dlogits = (softmax - onehot) * scale in one streaming pass.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPException.h>
 #include "common.h"
 
 namespace {
@@ -176,20 +177,52 @@ __global__ void ce_vp_bwd_kernel(const __hip_bfloat16* __restrict__ logits,
   }
 }
 
+// logits [rows, V] contiguous on the GPU; targets int64 [rows] beside them.
+// bf16 rows are read as 16-byte vectors, so V % 8 == 0 keeps every row aligned.
+void check_logits_targets(const at::Tensor& logits, const at::Tensor& targets, const char* who) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2,
+              who, ": logits must be a contiguous 2-D GPU tensor");
+  TORCH_CHECK(targets.device() == logits.device() && targets.scalar_type() == at::kLong &&
+                  targets.is_contiguous() && targets.dim() == 1 &&
+                  targets.size(0) == logits.size(0),
+              who, ": targets must be int64 [rows] on the logits' device");
+}
+
+void check_row_f32(const at::Tensor& t, const at::Tensor& logits, const char* who,
+                   const char* name) {
+  TORCH_CHECK(t.device() == logits.device() && t.scalar_type() == at::kFloat &&
+                  t.is_contiguous() && t.dim() == 1 && t.size(0) == logits.size(0),
+              who, ": ", name, " must be fp32 [rows] on the logits' device");
+}
+
+void check_scale(const at::Tensor& scale, const at::Tensor& logits, const char* who) {
+  TORCH_CHECK(scale.device() == logits.device() && scale.numel() == 1, who,
+              ": scale must be one element on the logits' device");
+}
+
+void check_vp_logits(const at::Tensor& logits, const char* who) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2 &&
+                  logits.scalar_type() == at::kBFloat16,
+              who, ": logits must be a contiguous 2-D bf16 GPU tensor");
+  TORCH_CHECK(logits.size(1) % 8 == 0, "ce_vp: vocab shard must be a multiple of 8");
+}
+
 }  // namespace
 
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets, long ignore_index) {
-  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2);
-  TORCH_CHECK(targets.scalar_type() == at::kLong);
+  check_logits_targets(logits, targets, "ce_fwd");
   const long rows = logits.size(0);
   const int V = logits.size(1);
-  auto loss_sum = at::empty({}, logits.options().dtype(at::kFloat));
+  TORCH_CHECK(logits.scalar_type() != at::kBFloat16 || V % 8 == 0,
+              "ce_fwd: bf16 vocab must be a multiple of 8");
+  auto loss_sum = at::zeros({}, logits.options().dtype(at::kFloat));
   auto ntok = at::zeros({}, logits.options().dtype(at::kLong));
   auto lse = at::empty({rows}, logits.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentHIPStream();
   constexpr int BLOCK = 256;
   const long grid = std::min<long>(rows, 4096);
   auto partials = at::empty({grid}, logits.options().dtype(at::kFloat));
+  if (rows == 0) return {loss_sum, ntok, lse};  // an empty grid is a launch error
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, logits.scalar_type(), "ce_fwd", [&] {
     using T = std::conditional_t<std::is_same_v<scalar_t, at::BFloat16>, __hip_bfloat16, float>;
     if constexpr (std::is_same_v<scalar_t, at::BFloat16> || std::is_same_v<scalar_t, float>) {
@@ -197,22 +230,27 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets, long ignor
           reinterpret_cast<const T*>(logits.data_ptr()), targets.data_ptr<long>(),
           partials.data_ptr<float>(), ntok.data_ptr<long>(), lse.data_ptr<float>(),
           rows, V, ignore_index);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
       TORCH_CHECK(false, "ce: unsupported dtype");
     }
   });
   reduce_partials_kernel<256><<<1, 256, 0, stream>>>(
       partials.data_ptr<float>(), (int)grid, loss_sum.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {loss_sum, ntok, lse};
 }
 
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Tensor scale,
                   long ignore_index) {
-  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous());
+  check_logits_targets(logits, targets, "ce_bwd");
+  check_row_f32(lse, logits, "ce_bwd", "lse");
+  check_scale(scale, logits, "ce_bwd");
   const long rows = logits.size(0);
   const int V = logits.size(1);
   TORCH_CHECK(V % 8 == 0, "ce_bwd: vocab must be a multiple of 8");
   auto dlogits = at::empty_like(logits);
+  if (logits.numel() == 0) return dlogits;
   auto stream = at::cuda::getCurrentHIPStream();
   auto scale_f = scale.to(at::kFloat);
   const int block = 256;
@@ -224,6 +262,7 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Ten
           reinterpret_cast<const T*>(logits.data_ptr()), targets.data_ptr<long>(),
           lse.data_ptr<float>(), scale_f.data_ptr<float>(),
           reinterpret_cast<T*>(dlogits.data_ptr()), rows, V, ignore_index);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
       TORCH_CHECK(false, "ce: unsupported dtype");
     }
@@ -233,39 +272,50 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Ten
 
 std::vector<at::Tensor> ce_vp_stats(at::Tensor logits, at::Tensor targets, long v0,
                                     long ignore_index) {
-  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2 &&
-              logits.scalar_type() == at::kBFloat16);
+  check_vp_logits(logits, "ce_vp_stats");
+  check_logits_targets(logits, targets, "ce_vp_stats");
   const long rows = logits.size(0);
   const int V = logits.size(1);
-  TORCH_CHECK(V % 8 == 0, "ce_vp: vocab shard must be a multiple of 8");
   auto m = at::empty({rows}, logits.options().dtype(at::kFloat));
   auto tgt = at::empty({rows}, logits.options().dtype(at::kFloat));
+  if (rows == 0) return {m, tgt};
   auto stream = at::cuda::getCurrentHIPStream();
   const int grid = (int)std::min<long>(rows, 2048);
   ce_vp_stats_kernel<256><<<grid, 256, 0, stream>>>(
       reinterpret_cast<const __hip_bfloat16*>(logits.data_ptr()),
       targets.data_ptr<long>(), m.data_ptr<float>(), tgt.data_ptr<float>(),
       rows, V, v0, ignore_index);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {m, tgt};
 }
 
 at::Tensor ce_vp_sumexp(at::Tensor logits, at::Tensor m_group) {
+  check_vp_logits(logits, "ce_vp_sumexp");
+  check_row_f32(m_group, logits, "ce_vp_sumexp", "m_group");
   const long rows = logits.size(0);
   const int V = logits.size(1);
   auto se = at::empty({rows}, logits.options().dtype(at::kFloat));
+  if (rows == 0) return se;
   auto stream = at::cuda::getCurrentHIPStream();
   const int grid = (int)std::min<long>(rows, 2048);
   ce_vp_sumexp_kernel<256><<<grid, 256, 0, stream>>>(
       reinterpret_cast<const __hip_bfloat16*>(logits.data_ptr()),
       m_group.data_ptr<float>(), se.data_ptr<float>(), rows, V);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return se;
 }
 
 at::Tensor ce_vp_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
                      at::Tensor scale, long v0, long ignore_index) {
+  check_vp_logits(logits, "ce_vp_bwd");
+  check_logits_targets(logits, targets, "ce_vp_bwd");
+  check_row_f32(lse, logits, "ce_vp_bwd", "lse");
+  check_scale(scale, logits, "ce_vp_bwd");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "ce_vp_bwd: scale must be fp32");
   const long rows = logits.size(0);
   const int V = logits.size(1);
   auto dl = at::empty_like(logits);
+  if (logits.numel() == 0) return dl;
   auto stream = at::cuda::getCurrentHIPStream();
   const long work = rows * (V / 8);
   const int grid = (int)std::min<long>((work + 255) / 256, 4096);
@@ -273,5 +323,6 @@ at::Tensor ce_vp_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
       reinterpret_cast<const __hip_bfloat16*>(logits.data_ptr()),
       targets.data_ptr<long>(), lse.data_ptr<float>(), scale.data_ptr<float>(),
       reinterpret_cast<__hip_bfloat16*>(dl.data_ptr()), rows, V, v0, ignore_index);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return dl;
 }

@@ -9,6 +9,7 @@
 // with saturation — exactly torch.float8_e4m3fn.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPException.h>
 #include "common.h"
 
 namespace {
@@ -124,22 +125,34 @@ std::vector<at::Tensor> fp8_quantize_pre(at::Tensor x, at::Tensor amax_in, bool 
   auto scale = at::empty({}, x.options().dtype(at::kFloat));
   const long grid = std::min<long>(cdiv(n, 256 * 8), 2048);
   auto* xp = reinterpret_cast<const __hip_bfloat16*>(xc.data_ptr());
+  if (n == 0) {  // nothing to cast: an empty grid is a launch error
+    TORCH_CHECK(!transpose || x.dim() == 2, "fp8_quantize transpose: 2D only");
+    auto y0 = transpose ? at::empty({x.size(1), x.size(0)}, xc.options().dtype(at::kFloat8_e4m3fn))
+                        : at::empty_like(xc, xc.options().dtype(at::kFloat8_e4m3fn));
+    return {y0, at::full({}, 1e-12f, x.options().dtype(at::kFloat))};
+  }
   if (have_amax) {
-    TORCH_CHECK(amax_in.scalar_type() == at::kFloat);
+    TORCH_CHECK(amax_in.scalar_type() == at::kFloat && amax_in.device() == x.device() &&
+                    amax_in.is_contiguous(),
+                "fp8_quantize_pre: amax partials must be contiguous fp32 on x's device");
     scale_from_partials_kernel<<<1, 256, 0, stream>>>(
         amax_in.data_ptr<float>(), amax_in.numel(), scale.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   } else {
     auto amax_bits = at::zeros({1}, x.options().dtype(at::kInt));
     amax_kernel<<<grid, 256, 0, stream>>>(
         xp, n, reinterpret_cast<unsigned*>(amax_bits.data_ptr<int>()));
+    C10_HIP_KERNEL_LAUNCH_CHECK();
     scale_from_amax_kernel<<<1, 1, 0, stream>>>(
         reinterpret_cast<unsigned*>(amax_bits.data_ptr<int>()), scale.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   at::Tensor y;
   if (!transpose) {
     y = at::empty_like(xc, xc.options().dtype(at::kFloat8_e4m3fn));
     cast_e4m3_kernel<<<grid, 256, 0, stream>>>(
         xp, reinterpret_cast<unsigned char*>(y.data_ptr()), n, scale.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   } else {
     TORCH_CHECK(x.dim() == 2, "fp8_quantize transpose: 2D only");
     const int N = x.size(0), K = x.size(1);
@@ -147,6 +160,7 @@ std::vector<at::Tensor> fp8_quantize_pre(at::Tensor x, at::Tensor amax_in, bool 
     dim3 g(cdiv(N, 32), cdiv(K, 32));
     cast_e4m3_t_kernel<<<g, 256, 0, stream>>>(
         xp, reinterpret_cast<unsigned char*>(y.data_ptr()), N, K, scale.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return {y, scale};
 }

@@ -202,7 +202,7 @@ at::Tensor gemv_ex(at::Tensor x, at::Tensor W, long mode, at::Tensor nw, double 
   sizes.back() = N;
   auto y = at::empty({B, N}, x.options());
   auto stream = at::cuda::getCurrentHIPStream();
-  const int grid_x = std::min(cdiv(N, 4), 2048);
+  const int grid_x = (int)std::min<long>(cdiv(N, 4), 2048);
   auto* Wp = reinterpret_cast<const __hip_bfloat16*>(W.data_ptr());
   auto* np = mode == 1 ? reinterpret_cast<const __hip_bfloat16*>(nw.contiguous().data_ptr())
                        : nullptr;
@@ -252,7 +252,7 @@ at::Tensor gemv_bf16(at::Tensor x, at::Tensor W) {
   sizes.back() = N;
   auto y = at::empty({B, N}, x.options());
   auto stream = at::cuda::getCurrentHIPStream();
-  const int grid_x = std::min(cdiv(N, 4), 2048);
+  const int grid_x = (int)std::min<long>(cdiv(N, 4), 2048);
   const size_t lds = (size_t)K * sizeof(__hip_bfloat16);
   TORCH_CHECK(lds <= 160 * 1024, "gemv: K too large for LDS staging");
   gemv_bf16_kernel<<<dim3(grid_x, B), 256, lds, stream>>>(

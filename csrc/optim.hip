@@ -5,6 +5,7 @@
 // device-resident sumsq — no host sync.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPException.h>
 #include "common.h"
 
 namespace {
@@ -74,7 +75,10 @@ __global__ void lion_kernel(P* __restrict__ param, float* __restrict__ master,
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
        i += gridDim.x * (long)blockDim.x) {
     const float g = to_f32(grad[i]) * cc;
-    const float upd = copysignf(1.f, b1 * m[i] + (1.f - b1) * g);
+    // sign(0) = 0, as in the torch path: an element with no gradient and no
+    // momentum (an unused embedding row) must not drift by lr every step
+    const float c = b1 * m[i] + (1.f - b1) * g;
+    const float upd = (c > 0.f) ? 1.f : (c < 0.f) ? -1.f : 0.f;
     m[i] = b2 * m[i] + (1.f - b2) * g;
     float p = master[i];
     if (wd > 0.f && i < decay_boundary) p *= (1.f - lr * wd);
@@ -113,10 +117,33 @@ void dispatch_pg(at::Tensor& param, at::Tensor& grad, F&& f) {
   else f(float{}, float{});
 }
 
+// Shared by the three step functions. The kernels index every buffer with the
+// same flat i < param.numel() and read the state through float*, so all of it
+// is checked here, before any launch. state = {master, moments...}.
+void check_step_args(const char* who, const at::Tensor& param, const at::Tensor& grad,
+                     std::initializer_list<const at::Tensor*> state, const at::Tensor& sumsq_t) {
+  TORCH_CHECK(param.is_cuda() && param.is_contiguous(), who, ": param must be a contiguous GPU tensor");
+  TORCH_CHECK(param.scalar_type() == at::kBFloat16 || param.scalar_type() == at::kFloat,
+              who, ": param must be bf16 or fp32");
+  const long n = param.numel();
+  TORCH_CHECK(grad.device() == param.device() && grad.is_contiguous() && grad.numel() == n &&
+                  (grad.scalar_type() == at::kBFloat16 || grad.scalar_type() == at::kFloat),
+              who, ": grad must be contiguous bf16 or fp32 with param's numel and device");
+  for (const at::Tensor* t : state)
+    TORCH_CHECK(t->device() == param.device() && t->is_contiguous() && t->numel() == n &&
+                    t->scalar_type() == at::kFloat,
+                who, ": master and moments must be contiguous fp32 with param's numel and device");
+  TORCH_CHECK(sumsq_t.device() == param.device() && sumsq_t.scalar_type() == at::kFloat &&
+                  sumsq_t.numel() == 1,
+              who, ": sumsq must be one fp32 element on param's device");
+}
+
 }  // namespace
 
 at::Tensor sumsq(at::Tensor g) {
-  TORCH_CHECK(g.is_cuda() && g.is_contiguous());
+  TORCH_CHECK(g.is_cuda() && g.is_contiguous() &&
+                  (g.scalar_type() == at::kBFloat16 || g.scalar_type() == at::kFloat),
+              "sumsq: g must be a contiguous bf16 or fp32 GPU tensor");
   auto out = at::empty({}, g.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentHIPStream();
   const long n = g.numel();
@@ -129,16 +156,19 @@ at::Tensor sumsq(at::Tensor g) {
   else
     sumsq_kernel<float><<<grid, block, 0, stream>>>(
         g.data_ptr<float>(), partials.data_ptr<float>(), n);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   reduce_partials_kernel<256><<<1, 256, 0, stream>>>(
       partials.data_ptr<float>(), (int)grid, out.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
 void adamw_step(at::Tensor param, at::Tensor master, at::Tensor grad, at::Tensor m,
                 at::Tensor v, at::Tensor sumsq_t, long step, double lr, double b1,
                 double b2, double eps, double wd, long decay_boundary, double max_norm) {
-  TORCH_CHECK(param.is_cuda() && param.is_contiguous() && master.is_contiguous());
+  check_step_args("adamw_step", param, grad, {&master, &m, &v}, sumsq_t);
   const long n = param.numel();
+  if (n == 0) return;  // an empty ZeRO-1 shard: an empty grid is a launch error
   auto stream = at::cuda::getCurrentHIPStream();
   const int block = 256;
   const long grid = std::min<long>(cdiv(n, block), 4096);
@@ -151,13 +181,16 @@ void adamw_step(at::Tensor param, at::Tensor master, at::Tensor grad, at::Tensor
         reinterpret_cast<const G*>(grad.data_ptr()), m.data_ptr<float>(), v.data_ptr<float>(),
         sumsq_t.data_ptr<float>(), n, decay_boundary, (float)lr, (float)b1, (float)b2,
         (float)eps, (float)wd, bc1, bc2, (float)max_norm);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   });
 }
 
 void lion_step(at::Tensor param, at::Tensor master, at::Tensor grad, at::Tensor m,
                at::Tensor sumsq_t, double lr, double b1, double b2, double wd,
                long decay_boundary, double max_norm) {
+  check_step_args("lion_step", param, grad, {&master, &m}, sumsq_t);
   const long n = param.numel();
+  if (n == 0) return;
   auto stream = at::cuda::getCurrentHIPStream();
   const int block = 256;
   const long grid = std::min<long>(cdiv(n, block), 4096);
@@ -168,13 +201,16 @@ void lion_step(at::Tensor param, at::Tensor master, at::Tensor grad, at::Tensor 
         reinterpret_cast<const G*>(grad.data_ptr()), m.data_ptr<float>(),
         sumsq_t.data_ptr<float>(), n, decay_boundary, (float)lr, (float)b1, (float)b2,
         (float)wd, (float)max_norm);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   });
 }
 
 void sgd_step(at::Tensor param, at::Tensor master, at::Tensor grad, at::Tensor buf,
               at::Tensor sumsq_t, double lr, double mom, double wd, long decay_boundary,
               bool nesterov, double max_norm) {
+  check_step_args("sgd_step", param, grad, {&master, &buf}, sumsq_t);
   const long n = param.numel();
+  if (n == 0) return;
   auto stream = at::cuda::getCurrentHIPStream();
   const int block = 256;
   const long grid = std::min<long>(cdiv(n, block), 4096);
@@ -185,5 +221,6 @@ void sgd_step(at::Tensor param, at::Tensor master, at::Tensor grad, at::Tensor b
         reinterpret_cast<const G*>(grad.data_ptr()), buf.data_ptr<float>(),
         sumsq_t.data_ptr<float>(), n, decay_boundary, (float)lr, (float)mom, (float)wd,
         nesterov, (float)max_norm);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   });
 }

@@ -3,6 +3,7 @@
 // Replaces /root/reference/models/llama.py:44-56 (Python-composed RMSNorm).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPException.h>
 #include "common.h"
 
 namespace {
@@ -29,7 +30,7 @@ __global__ void rmsnorm_fwd_kernel(const T* __restrict__ x, const T* __restrict_
 
   float ss = 0.f;
   if constexpr (sizeof(T) == 2) {
-    const int HV = H / 8;
+    const int HV = (H % 8 == 0) ? H / 8 : 0;  // ragged H: rows are not 16 B aligned
     const uint4* xv = reinterpret_cast<const uint4*>(xr);
     for (int i = threadIdx.x; i < HV; i += BLOCK) {
       U4 u; u.u = xv[i];
@@ -67,7 +68,7 @@ __global__ void rmsnorm_fwd_kernel(const T* __restrict__ x, const T* __restrict_
   const T* src = HAS_RES ? sr : xr;
   float am = 0.f;
   if constexpr (sizeof(T) == 2) {
-    const int HV = H / 8;
+    const int HV = (H % 8 == 0) ? H / 8 : 0;  // ragged H: rows are not 16 B aligned
     const uint4* xv = reinterpret_cast<const uint4*>(src);
     const uint4* wv = reinterpret_cast<const uint4*>(w);
     uint4* yv = reinterpret_cast<uint4*>(yr);
@@ -126,7 +127,7 @@ __global__ void rmsnorm_bwd_kernel(const T* __restrict__ x, const T* __restrict_
 
     float c = 0.f;
     if constexpr (sizeof(T) == 2) {
-      const int HV = H / 8;
+      const int HV = (H % 8 == 0) ? H / 8 : 0;  // ragged H: rows are not 16 B aligned
       const uint4* xv = reinterpret_cast<const uint4*>(xr);
       const uint4* dyv = reinterpret_cast<const uint4*>(dyr);
       const uint4* wv = reinterpret_cast<const uint4*>(w);
@@ -173,7 +174,9 @@ __global__ void rmsnorm_bwd_kernel(const T* __restrict__ x, const T* __restrict_
       for (int i = threadIdx.x; i < H; i += BLOCK) {
         const float xi = to_f32(xr[i]);
         const float dyi = to_f32(dyr[i]);
-        from_f32(&dxr[i], r * dyi * to_f32(w[i]) - xi * kk);
+        float o = r * dyi * to_f32(w[i]) - xi * kk;
+        if constexpr (HAS_DADD) o += to_f32(dar[i]);
+        from_f32(&dxr[i], o);
         dw_acc[i] += dyi * xi * r;
       }
     }
@@ -181,6 +184,22 @@ __global__ void rmsnorm_bwd_kernel(const T* __restrict__ x, const T* __restrict_
   }
   float* dwp = dw_partial + blockIdx.x * (long)H;
   for (int i = threadIdx.x; i < H; i += BLOCK) dwp[i] = dw_acc[i];
+}
+
+// The kernels read w, res, dy and dadd through a pointer type chosen from x
+// alone, so every tensor has to agree with x before anything is launched.
+void check_like_x(const at::Tensor& t, const at::Tensor& x, const char* name) {
+  TORCH_CHECK(t.device() == x.device(), "rmsnorm: ", name, " must be on x's device");
+  TORCH_CHECK(t.scalar_type() == x.scalar_type(), "rmsnorm: ", name, " must have x's dtype");
+  TORCH_CHECK(t.is_contiguous(), "rmsnorm: ", name, " must be contiguous");
+}
+
+void check_x_w(const at::Tensor& x, const at::Tensor& w) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() >= 1, "rmsnorm: x must be a contiguous GPU tensor");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat,
+              "rmsnorm: unsupported dtype");
+  check_like_x(w, x, "w");
+  TORCH_CHECK(w.numel() == x.size(-1), "rmsnorm: w must have H elements");
 }
 
 }  // namespace
@@ -191,10 +210,14 @@ __global__ void rmsnorm_bwd_kernel(const T* __restrict__ x, const T* __restrict_
 // max|y| (consumed by fp8_quantize_pre). Returns {y, rstd[, s][, amax]}.
 std::vector<at::Tensor> rmsnorm_fwd_res(at::Tensor x, at::Tensor res, at::Tensor w, double eps,
                                         bool with_amax) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous());
+  check_x_w(x, w);
   const bool has_res = res.numel() > 0;
-  if (has_res) TORCH_CHECK(res.is_contiguous() && res.sizes() == x.sizes());
+  if (has_res) {
+    check_like_x(res, x, "res");
+    TORCH_CHECK(res.sizes() == x.sizes(), "rmsnorm: res must have x's shape");
+  }
   const int H = x.size(-1);
+  TORCH_CHECK(H > 0, "rmsnorm: empty hidden dimension");
   const long rows = x.numel() / H;
   auto y = at::empty_like(x);
   auto s = has_res ? at::empty_like(x) : at::empty({0}, x.options());
@@ -205,6 +228,7 @@ std::vector<at::Tensor> rmsnorm_fwd_res(at::Tensor x, at::Tensor res, at::Tensor
   auto stream = at::cuda::getCurrentHIPStream();
   constexpr int BLOCK = 256;
   dim3 grid(rows);
+  if (rows > 0)  // an empty grid is a launch error, not a no-op
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, x.scalar_type(), "rmsnorm_fwd", [&] {
     using T = std::conditional_t<std::is_same_v<scalar_t, at::BFloat16>, __hip_bfloat16, float>;
     if constexpr (std::is_same_v<scalar_t, at::BFloat16> || std::is_same_v<scalar_t, float>) {
@@ -218,6 +242,7 @@ std::vector<at::Tensor> rmsnorm_fwd_res(at::Tensor x, at::Tensor res, at::Tensor
             reinterpret_cast<const T*>(x.data_ptr()), nullptr, nullptr,
             reinterpret_cast<const T*>(w.data_ptr()),
             reinterpret_cast<T*>(y.data_ptr()), rstd.data_ptr<float>(), H, (float)eps, ab);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
       TORCH_CHECK(false, "rmsnorm: unsupported dtype");
     }
@@ -235,11 +260,21 @@ std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
 // dadd numel()==0 -> plain; otherwise dx += dadd (fused residual grad add).
 std::vector<at::Tensor> rmsnorm_bwd_add(at::Tensor x, at::Tensor w, at::Tensor rstd,
                                         at::Tensor dy, at::Tensor dadd) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && dy.is_contiguous());
+  check_x_w(x, w);
+  check_like_x(dy, x, "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes(), "rmsnorm: dy must have x's shape");
   const bool has_dadd = dadd.numel() > 0;
-  if (has_dadd) TORCH_CHECK(dadd.is_contiguous() && dadd.sizes() == x.sizes());
+  if (has_dadd) {
+    check_like_x(dadd, x, "dadd");
+    TORCH_CHECK(dadd.sizes() == x.sizes(), "rmsnorm: dadd must have x's shape");
+  }
   const int H = x.size(-1);
+  TORCH_CHECK(H > 0, "rmsnorm: empty hidden dimension");
   const long rows = x.numel() / H;
+  TORCH_CHECK(rstd.device() == x.device() && rstd.scalar_type() == at::kFloat &&
+                  rstd.is_contiguous() && rstd.numel() == rows,
+              "rmsnorm: rstd must be fp32 with one entry per row, on x's device");
+  if (rows == 0) return {at::empty_like(x), at::zeros({H}, x.options().dtype(at::kFloat))};
   auto dx = at::empty_like(x);
   constexpr int BLOCK = 256;
   const int nblocks = (int)std::min<long>(rows, 1024);
@@ -260,6 +295,7 @@ std::vector<at::Tensor> rmsnorm_bwd_add(at::Tensor x, at::Tensor w, at::Tensor r
             reinterpret_cast<const T*>(x.data_ptr()), reinterpret_cast<const T*>(w.data_ptr()),
             rstd.data_ptr<float>(), reinterpret_cast<const T*>(dy.data_ptr()), nullptr,
             reinterpret_cast<T*>(dx.data_ptr()), dw_partial.data_ptr<float>(), rows, H);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
       TORCH_CHECK(false, "rmsnorm: unsupported dtype");
     }

@@ -4,6 +4,7 @@
 // sampler wrapper routes here only when top_p == 1.)
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPException.h>
 #include "common.h"
 
 namespace {
@@ -104,11 +105,13 @@ void sample_token_dev(at::Tensor logits, at::Tensor out, double temperature,
   TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2);
   TORCH_CHECK(logits.scalar_type() == at::kBFloat16);
   const int B = logits.size(0), V = logits.size(1);
+  if (B == 0) return;  // an empty grid is a launch error
   auto stream = at::cuda::getCurrentHIPStream();
   sample_dev_kernel<<<B, 256, 0, stream>>>(
       reinterpret_cast<const __hip_bfloat16*>(logits.data_ptr()),
       out.data_ptr<long>(), V, (float)(1.0 / temperature), (float)min_p,
       (unsigned)seed, pos.data_ptr<int>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 at::Tensor sample_token(at::Tensor logits, double temperature, double top_p, double min_p,
@@ -121,5 +124,6 @@ at::Tensor sample_token(at::Tensor logits, double temperature, double top_p, dou
   sample_kernel<<<1, 256, 0, stream>>>(logits.data_ptr<float>(), out.data_ptr<long>(),
                                        (int)logits.numel(), (float)(1.0 / temperature),
                                        (float)min_p, (unsigned)seed);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }

@@ -2,6 +2,7 @@
 // on the [.., 2I] output of the fused gate+up GEMM. HBM-bound: bf16x8 loads.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPException.h>
 #include "common.h"
 
 namespace {
@@ -97,9 +98,9 @@ __global__ void swiglu_bwd_kernel(const T* __restrict__ gu, const T* __restrict_
 }  // namespace
 
 std::vector<at::Tensor> swiglu_fwd_amax(at::Tensor gu, bool with_amax) {
-  TORCH_CHECK(gu.is_cuda() && gu.is_contiguous());
+  TORCH_CHECK(gu.is_cuda() && gu.is_contiguous() && gu.dim() >= 1);
   const int I2 = gu.size(-1);
-  TORCH_CHECK(I2 % 16 == 0, "swiglu: intermediate size must be a multiple of 8");
+  TORCH_CHECK(I2 > 0 && I2 % 16 == 0, "swiglu: intermediate size must be a multiple of 8");
   const int I = I2 / 2;
   const long rows = gu.numel() / I2;
   auto sizes = gu.sizes().vec();
@@ -111,12 +112,14 @@ std::vector<at::Tensor> swiglu_fwd_amax(at::Tensor gu, bool with_amax) {
   const long grid = std::min<long>(cdiv(total, block), 2048);
   auto amax = with_amax ? at::empty({grid}, gu.options().dtype(at::kFloat))
                         : at::empty({0}, gu.options().dtype(at::kFloat));
+  if (total == 0) return {out, amax};  // an empty grid is a launch error
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, gu.scalar_type(), "swiglu_fwd", [&] {
     using T = std::conditional_t<std::is_same_v<scalar_t, at::BFloat16>, __hip_bfloat16, float>;
     if constexpr (std::is_same_v<scalar_t, at::BFloat16> || std::is_same_v<scalar_t, float>) {
       swiglu_fwd_kernel<T><<<grid, block, 0, stream>>>(
           reinterpret_cast<const T*>(gu.data_ptr()), reinterpret_cast<T*>(out.data_ptr()), rows, I,
           with_amax ? amax.data_ptr<float>() : nullptr);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
       TORCH_CHECK(false, "swiglu: unsupported dtype");
     }
@@ -129,11 +132,19 @@ at::Tensor swiglu_fwd(at::Tensor gu) {
 }
 
 at::Tensor swiglu_bwd(at::Tensor gu, at::Tensor dy) {
-  TORCH_CHECK(gu.is_cuda() && gu.is_contiguous() && dy.is_contiguous());
+  TORCH_CHECK(gu.is_cuda() && gu.is_contiguous() && gu.dim() >= 1);
   const int I2 = gu.size(-1);
+  TORCH_CHECK(I2 > 0 && I2 % 16 == 0, "swiglu: intermediate size must be a multiple of 8");
   const int I = I2 / 2;
   const long rows = gu.numel() / I2;
+  // dy is read through gu's element type, [..., I] rows laid out like gu's
+  TORCH_CHECK(dy.device() == gu.device() && dy.scalar_type() == gu.scalar_type() &&
+                  dy.is_contiguous(),
+              "swiglu_bwd: dy must be contiguous with gu's dtype and device");
+  TORCH_CHECK(dy.dim() == gu.dim() && dy.size(-1) == I && dy.numel() == rows * I,
+              "swiglu_bwd: dy must be [..., I]");
   auto dgu = at::empty_like(gu);
+  if (gu.numel() == 0) return dgu;
   auto stream = at::cuda::getCurrentHIPStream();
   const long total = rows * (I / 8);
   const int block = 256;
@@ -144,6 +155,7 @@ at::Tensor swiglu_bwd(at::Tensor gu, at::Tensor dy) {
       swiglu_bwd_kernel<T><<<grid, block, 0, stream>>>(
           reinterpret_cast<const T*>(gu.data_ptr()), reinterpret_cast<const T*>(dy.data_ptr()),
           reinterpret_cast<T*>(dgu.data_ptr()), rows, I);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
       TORCH_CHECK(false, "swiglu: unsupported dtype");
     }

@@ -12,6 +12,13 @@ import torch
 from ._ext import get_ext, use_hip
 
 
+def _w_like(weight: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """The kernels read the weight through x's element type: hand them one of
+    x's dtype (an fp32 norm weight under a bf16 activation is cast here; the
+    returned dw is cast back to the weight's dtype by the caller)."""
+    return (weight if weight.dtype == x.dtype else weight.to(x.dtype)).contiguous()
+
+
 def rms_norm_ref(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
     """Pure-torch reference (fp32 accumulation, same contract as the kernel)."""
     xf = x.float()
@@ -27,11 +34,11 @@ class _RMSNormFn(torch.autograd.Function):
             ext = get_ext()
             if emit_amax:
                 y, rstd, amax = ext.rmsnorm_fwd_res(
-                    x.contiguous(), x.new_empty(0), weight.contiguous(), eps, True
+                    x.contiguous(), x.new_empty(0), _w_like(weight, x), eps, True
                 )
                 y._mcdp_amax = amax  # fp8 quantizer skips its amax pass
             else:
-                y, rstd = ext.rmsnorm_fwd(x.contiguous(), weight.contiguous(), eps)
+                y, rstd = ext.rmsnorm_fwd(x.contiguous(), _w_like(weight, x), eps)
             ctx.save_for_backward(x, weight, rstd)
             ctx.eps = eps
             ctx.hip = True
@@ -51,7 +58,7 @@ class _RMSNormFn(torch.autograd.Function):
         if ctx.hip:
             ext = get_ext()
             dx, dw = ext.rmsnorm_bwd(
-                x.contiguous(), weight.contiguous(), rstd, dy.contiguous()
+                x.contiguous(), _w_like(weight, x), rstd, dy.contiguous()
             )
             return dx, dw.to(weight.dtype), None, None
         xf = x.float()
@@ -98,7 +105,7 @@ class _AddRMSNormFn(torch.autograd.Function):
         if use_hip(x, res, weight):
             ext = get_ext()
             out = ext.rmsnorm_fwd_res(
-                x.contiguous(), res.contiguous(), weight.contiguous(), eps, emit_amax
+                x.contiguous(), res.contiguous(), _w_like(weight, x), eps, emit_amax
             )
             y, rstd, s = out[0], out[1], out[2]
             if emit_amax:
@@ -121,7 +128,7 @@ class _AddRMSNormFn(torch.autograd.Function):
             ext = get_ext()
             dadd = ds.contiguous() if ds is not None else s.new_empty(0)
             dx, dw = ext.rmsnorm_bwd_add(
-                s.contiguous(), weight.contiguous(), rstd, dy.contiguous(), dadd
+                s.contiguous(), _w_like(weight, s), rstd, dy.contiguous(), dadd
             )
             # s = x + res: both inputs get the same gradient tensor
             return dx, dx, dw.to(weight.dtype), None, None

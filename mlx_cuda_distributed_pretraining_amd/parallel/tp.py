@@ -323,7 +323,8 @@ def vocab_parallel_cross_entropy(logits_local: torch.Tensor, targets: torch.Tens
     gradient."""
     if (logits_local.is_cuda and logits_local.dtype == torch.bfloat16
             and logits_local.is_contiguous() and logits_local.shape[1] % 8 == 0):
-        return _VPCrossEntropyHIP.apply(logits_local, targets, int(v0), int(ignore_index))
+        return _VPCrossEntropyHIP.apply(logits_local, targets.contiguous(), int(v0),
+                                        int(ignore_index))
     lf = logits_local.float()
     n, v_loc = lf.shape
     mask = targets != ignore_index
