@@ -31,6 +31,11 @@ at::Tensor ce_vp_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets, long ignore_index);
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Tensor scale,
                   long ignore_index);
+std::vector<at::Tensor> ce_fwd_z(at::Tensor logits, at::Tensor targets, long ignore_index);
+at::Tensor ce_bwd_z(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Tensor scale_ce,
+                    at::Tensor scale_z, long ignore_index);
+at::Tensor ce_vp_bwd_z(at::Tensor logits, at::Tensor targets, at::Tensor lse,
+                       at::Tensor scale_ce, at::Tensor scale_z, long v0, long ignore_index);
 // optim.hip
 at::Tensor sumsq(at::Tensor g);
 void adamw_step(at::Tensor param, at::Tensor master, at::Tensor grad, at::Tensor m,
@@ -124,6 +129,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_vp_sumexp", &ce_vp_sumexp, "vocab-parallel CE pass 2 (sum exp)");
   m.def("ce_vp_bwd", &ce_vp_bwd, "vocab-parallel CE backward (dlogits)");
   m.def("ce_bwd", &ce_bwd, "fused cross-entropy backward (dlogits)");
+  m.def("ce_fwd_z", &ce_fwd_z, "cross-entropy + z-loss forward (loss_sum, z_sum, ntok, lse)");
+  m.def("ce_bwd_z", &ce_bwd_z, "cross-entropy + z-loss backward (dlogits)");
+  m.def("ce_vp_bwd_z", &ce_vp_bwd_z, "vocab-parallel cross-entropy + z-loss backward (dlogits)");
   m.def("sumsq", &sumsq, "sum of squares -> f32 scalar");
   m.def("adamw_step", &adamw_step, "fused AdamW over flat buffers");
   m.def("lion_step", &lion_step, "fused Lion over flat buffers");

@@ -10,15 +10,21 @@
 
 namespace {
 
-template <typename T, int BLOCK>
+// Z adds the auxiliary z-loss sum: lse^2 over the counted rows, squared in
+// fp32 from the lse that is stored, into a second partial per block that goes
+// through the same fixed-order reduction as the loss. Without Z the kernel is
+// the plain forward, instruction for instruction.
+template <typename T, int BLOCK, bool Z>
 __global__ void ce_fwd_kernel(const T* __restrict__ logits, const long* __restrict__ targets,
-                              float* __restrict__ loss_partials, long* __restrict__ ntok,
-                              float* __restrict__ lse_out, long rows, int V, long ignore_index) {
+                              float* __restrict__ loss_partials, float* __restrict__ z_partials,
+                              long* __restrict__ ntok, float* __restrict__ lse_out, long rows,
+                              int V, long ignore_index) {
   __shared__ float scratch[BLOCK / WAVE];
   // thread 0 adds this block's rows in row order; reduce_partials_kernel then
   // adds the per-block partials in a fixed order, so the loss is the same
   // every run (the integer token count is order-independent as an atomic)
   float block_loss = 0.f;
+  float block_z = 0.f;
   for (long row = blockIdx.x; row < rows; row += gridDim.x) {
     const T* lr = logits + row * (long)V;
     // pass 1: max
@@ -57,18 +63,29 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits, const long* __restri
       const long t = targets[row];
       if (t != ignore_index) {
         block_loss += lse - to_f32(lr[t]);
+        if constexpr (Z) block_z += lse * lse;
         atomicAdd(reinterpret_cast<unsigned long long*>(ntok), 1ull);
       }
     }
   }
-  if (threadIdx.x == 0) loss_partials[blockIdx.x] = block_loss;
+  if (threadIdx.x == 0) {
+    loss_partials[blockIdx.x] = block_loss;
+    if constexpr (Z) z_partials[blockIdx.x] = block_z;
+  }
 }
 
-template <typename T>
+// Z: with a = *scale and b = *scale_z the row also carries the z-loss term,
+// dlogits = (p - onehot) * a + p * (b * lse). The CE part is the plain
+// kernel's own expression and the z part is added to it in one fma, so b = 0
+// gives the plain kernel's bits.
+template <typename T, bool Z>
 __global__ void ce_bwd_kernel(const T* __restrict__ logits, const long* __restrict__ targets,
                               const float* __restrict__ lse, const float* __restrict__ scale,
-                              T* __restrict__ dlogits, long rows, int V, long ignore_index) {
+                              const float* __restrict__ scale_z, T* __restrict__ dlogits,
+                              long rows, int V, long ignore_index) {
   const float sc = *scale;
+  float sz = 0.f;
+  if constexpr (Z) sz = *scale_z;
   const int VV = V / 8;
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < rows * (long)VV;
        idx += gridDim.x * (long)blockDim.x) {
@@ -83,11 +100,18 @@ __global__ void ce_bwd_kernel(const T* __restrict__ logits, const long* __restri
       for (int j = 0; j < 8; ++j) from_f32(&dr[j], 0.f);
       continue;
     }
+    const float zl = sz * l;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float p = __expf(to_f32(lr[j]) - l);
-      if (col + j == (int)t) p -= 1.f;
-      from_f32(&dr[j], p * sc);
+      if constexpr (Z) {
+        const float pz = p * zl;
+        if (col + j == (int)t) p -= 1.f;
+        from_f32(&dr[j], fmaf(p, sc, pz));
+      } else {
+        if (col + j == (int)t) p -= 1.f;
+        from_f32(&dr[j], p * sc);
+      }
     }
   }
 }
@@ -146,13 +170,18 @@ __global__ void ce_vp_sumexp_kernel(const __hip_bfloat16* __restrict__ logits,
 
 // Backward: dlogits = (exp(l - lse_group) - onehot(t - v0)) * (*scale), rows
 // with ignored targets get 0 (scale = upstream_grad / ntok, device scalar).
+// Z adds p * (*scale_z * lse_group), as in ce_bwd_kernel.
+template <bool Z>
 __global__ void ce_vp_bwd_kernel(const __hip_bfloat16* __restrict__ logits,
                                  const long* __restrict__ targets,
                                  const float* __restrict__ lse,
                                  const float* __restrict__ scale,
+                                 const float* __restrict__ scale_z,
                                  __hip_bfloat16* __restrict__ dlogits,
                                  long rows, int V, long v0, long ignore_index) {
   const float sc = *scale;
+  float sz = 0.f;
+  if constexpr (Z) sz = *scale_z;
   const int VV = V / 8;
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < rows * (long)VV;
        idx += gridDim.x * (long)blockDim.x) {
@@ -168,11 +197,18 @@ __global__ void ce_vp_bwd_kernel(const __hip_bfloat16* __restrict__ logits,
       continue;
     }
     const long tl = t - v0;
+    const float zl = sz * l;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float p = __expf(to_f32(lr[j]) - l);
-      if (col + j == (int)tl) p -= 1.f;
-      from_f32(&dr[j], p * sc);
+      if constexpr (Z) {
+        const float pz = p * zl;
+        if (col + j == (int)tl) p -= 1.f;
+        from_f32(&dr[j], fmaf(p, sc, pz));
+      } else {
+        if (col + j == (int)tl) p -= 1.f;
+        from_f32(&dr[j], p * sc);
+      }
     }
   }
 }
@@ -207,29 +243,44 @@ void check_vp_logits(const at::Tensor& logits, const char* who) {
   TORCH_CHECK(logits.size(1) % 8 == 0, "ce_vp: vocab shard must be a multiple of 8");
 }
 
-}  // namespace
+// the two scales of the z backward are read as float by the kernel
+void check_scale_f32(const at::Tensor& scale, const at::Tensor& logits, const char* who,
+                     const char* name) {
+  TORCH_CHECK(scale.device() == logits.device() && scale.numel() == 1 &&
+                  scale.scalar_type() == at::kFloat,
+              who, ": ", name, " must be one fp32 element on the logits' device");
+}
 
-std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets, long ignore_index) {
-  check_logits_targets(logits, targets, "ce_fwd");
+// {loss_sum, ntok, lse}, and z_sum after loss_sum when Z
+template <bool Z>
+std::vector<at::Tensor> ce_fwd_impl(const at::Tensor& logits, const at::Tensor& targets,
+                                    long ignore_index, const char* who) {
+  check_logits_targets(logits, targets, who);
   const long rows = logits.size(0);
   const int V = logits.size(1);
   TORCH_CHECK(logits.scalar_type() != at::kBFloat16 || V % 8 == 0,
-              "ce_fwd: bf16 vocab must be a multiple of 8");
+              who, ": bf16 vocab must be a multiple of 8");
   auto loss_sum = at::zeros({}, logits.options().dtype(at::kFloat));
+  at::Tensor z_sum, z_partials;
+  if constexpr (Z) z_sum = at::zeros({}, logits.options().dtype(at::kFloat));
   auto ntok = at::zeros({}, logits.options().dtype(at::kLong));
   auto lse = at::empty({rows}, logits.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentHIPStream();
   constexpr int BLOCK = 256;
   const long grid = std::min<long>(rows, 4096);
   auto partials = at::empty({grid}, logits.options().dtype(at::kFloat));
-  if (rows == 0) return {loss_sum, ntok, lse};  // an empty grid is a launch error
+  if constexpr (Z) z_partials = at::empty({grid}, logits.options().dtype(at::kFloat));
+  if (rows == 0) {  // an empty grid is a launch error
+    if constexpr (Z) return {loss_sum, z_sum, ntok, lse};
+    return {loss_sum, ntok, lse};
+  }
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, logits.scalar_type(), "ce_fwd", [&] {
     using T = std::conditional_t<std::is_same_v<scalar_t, at::BFloat16>, __hip_bfloat16, float>;
     if constexpr (std::is_same_v<scalar_t, at::BFloat16> || std::is_same_v<scalar_t, float>) {
-      ce_fwd_kernel<T, BLOCK><<<grid, BLOCK, 0, stream>>>(
+      ce_fwd_kernel<T, BLOCK, Z><<<grid, BLOCK, 0, stream>>>(
           reinterpret_cast<const T*>(logits.data_ptr()), targets.data_ptr<long>(),
-          partials.data_ptr<float>(), ntok.data_ptr<long>(), lse.data_ptr<float>(),
-          rows, V, ignore_index);
+          partials.data_ptr<float>(), Z ? z_partials.data_ptr<float>() : nullptr,
+          ntok.data_ptr<long>(), lse.data_ptr<float>(), rows, V, ignore_index);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
       TORCH_CHECK(false, "ce: unsupported dtype");
@@ -238,29 +289,34 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets, long ignor
   reduce_partials_kernel<256><<<1, 256, 0, stream>>>(
       partials.data_ptr<float>(), (int)grid, loss_sum.data_ptr<float>());
   C10_HIP_KERNEL_LAUNCH_CHECK();
+  if constexpr (Z) {
+    reduce_partials_kernel<256><<<1, 256, 0, stream>>>(
+        z_partials.data_ptr<float>(), (int)grid, z_sum.data_ptr<float>());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    return {loss_sum, z_sum, ntok, lse};
+  }
   return {loss_sum, ntok, lse};
 }
 
-at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Tensor scale,
-                  long ignore_index) {
-  check_logits_targets(logits, targets, "ce_bwd");
-  check_row_f32(lse, logits, "ce_bwd", "lse");
-  check_scale(scale, logits, "ce_bwd");
+// the arguments are checked by the callers; scale_z is read only when Z
+template <bool Z>
+at::Tensor ce_bwd_impl(const at::Tensor& logits, const at::Tensor& targets,
+                       const at::Tensor& lse, const float* scale, const float* scale_z,
+                       long ignore_index, const char* who) {
   const long rows = logits.size(0);
   const int V = logits.size(1);
-  TORCH_CHECK(V % 8 == 0, "ce_bwd: vocab must be a multiple of 8");
+  TORCH_CHECK(V % 8 == 0, who, ": vocab must be a multiple of 8");
   auto dlogits = at::empty_like(logits);
   if (logits.numel() == 0) return dlogits;
   auto stream = at::cuda::getCurrentHIPStream();
-  auto scale_f = scale.to(at::kFloat);
   const int block = 256;
   const long grid = std::min<long>(cdiv(rows * (V / 8), block), 4096);
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, logits.scalar_type(), "ce_bwd", [&] {
     using T = std::conditional_t<std::is_same_v<scalar_t, at::BFloat16>, __hip_bfloat16, float>;
     if constexpr (std::is_same_v<scalar_t, at::BFloat16> || std::is_same_v<scalar_t, float>) {
-      ce_bwd_kernel<T><<<grid, block, 0, stream>>>(
+      ce_bwd_kernel<T, Z><<<grid, block, 0, stream>>>(
           reinterpret_cast<const T*>(logits.data_ptr()), targets.data_ptr<long>(),
-          lse.data_ptr<float>(), scale_f.data_ptr<float>(),
+          lse.data_ptr<float>(), scale, scale_z,
           reinterpret_cast<T*>(dlogits.data_ptr()), rows, V, ignore_index);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
@@ -268,6 +324,58 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Ten
     }
   });
   return dlogits;
+}
+
+template <bool Z>
+at::Tensor ce_vp_bwd_impl(const at::Tensor& logits, const at::Tensor& targets,
+                          const at::Tensor& lse, const float* scale, const float* scale_z,
+                          long v0, long ignore_index) {
+  const long rows = logits.size(0);
+  const int V = logits.size(1);
+  auto dl = at::empty_like(logits);
+  if (logits.numel() == 0) return dl;
+  auto stream = at::cuda::getCurrentHIPStream();
+  const long work = rows * (V / 8);
+  const int grid = (int)std::min<long>((work + 255) / 256, 4096);
+  ce_vp_bwd_kernel<Z><<<grid, 256, 0, stream>>>(
+      reinterpret_cast<const __hip_bfloat16*>(logits.data_ptr()),
+      targets.data_ptr<long>(), lse.data_ptr<float>(), scale, scale_z,
+      reinterpret_cast<__hip_bfloat16*>(dl.data_ptr()), rows, V, v0, ignore_index);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return dl;
+}
+
+}  // namespace
+
+std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets, long ignore_index) {
+  return ce_fwd_impl<false>(logits, targets, ignore_index, "ce_fwd");
+}
+
+// (loss_sum, z_sum, ntok, lse): z_sum = sum of lse^2 over the counted rows
+std::vector<at::Tensor> ce_fwd_z(at::Tensor logits, at::Tensor targets, long ignore_index) {
+  return ce_fwd_impl<true>(logits, targets, ignore_index, "ce_fwd_z");
+}
+
+at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Tensor scale,
+                  long ignore_index) {
+  check_logits_targets(logits, targets, "ce_bwd");
+  check_row_f32(lse, logits, "ce_bwd", "lse");
+  check_scale(scale, logits, "ce_bwd");
+  auto scale_f = scale.to(at::kFloat);
+  return ce_bwd_impl<false>(logits, targets, lse, scale_f.data_ptr<float>(), nullptr,
+                            ignore_index, "ce_bwd");
+}
+
+// dlogits = p * (a + b * lse) - a * onehot with a = *scale_ce (g_ce / ntok) and
+// b = *scale_z (2 * g_z / ntok), both fp32 device scalars
+at::Tensor ce_bwd_z(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Tensor scale_ce,
+                    at::Tensor scale_z, long ignore_index) {
+  check_logits_targets(logits, targets, "ce_bwd_z");
+  check_row_f32(lse, logits, "ce_bwd_z", "lse");
+  check_scale_f32(scale_ce, logits, "ce_bwd_z", "scale_ce");
+  check_scale_f32(scale_z, logits, "ce_bwd_z", "scale_z");
+  return ce_bwd_impl<true>(logits, targets, lse, scale_ce.data_ptr<float>(),
+                           scale_z.data_ptr<float>(), ignore_index, "ce_bwd_z");
 }
 
 std::vector<at::Tensor> ce_vp_stats(at::Tensor logits, at::Tensor targets, long v0,
@@ -312,17 +420,18 @@ at::Tensor ce_vp_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
   check_row_f32(lse, logits, "ce_vp_bwd", "lse");
   check_scale(scale, logits, "ce_vp_bwd");
   TORCH_CHECK(scale.scalar_type() == at::kFloat, "ce_vp_bwd: scale must be fp32");
-  const long rows = logits.size(0);
-  const int V = logits.size(1);
-  auto dl = at::empty_like(logits);
-  if (logits.numel() == 0) return dl;
-  auto stream = at::cuda::getCurrentHIPStream();
-  const long work = rows * (V / 8);
-  const int grid = (int)std::min<long>((work + 255) / 256, 4096);
-  ce_vp_bwd_kernel<<<grid, 256, 0, stream>>>(
-      reinterpret_cast<const __hip_bfloat16*>(logits.data_ptr()),
-      targets.data_ptr<long>(), lse.data_ptr<float>(), scale.data_ptr<float>(),
-      reinterpret_cast<__hip_bfloat16*>(dl.data_ptr()), rows, V, v0, ignore_index);
-  C10_HIP_KERNEL_LAUNCH_CHECK();
-  return dl;
+  return ce_vp_bwd_impl<false>(logits, targets, lse, scale.data_ptr<float>(), nullptr, v0,
+                               ignore_index);
+}
+
+// the shard's part of the z backward (ce_bwd_z), lse being the group's
+at::Tensor ce_vp_bwd_z(at::Tensor logits, at::Tensor targets, at::Tensor lse,
+                       at::Tensor scale_ce, at::Tensor scale_z, long v0, long ignore_index) {
+  check_vp_logits(logits, "ce_vp_bwd_z");
+  check_logits_targets(logits, targets, "ce_vp_bwd_z");
+  check_row_f32(lse, logits, "ce_vp_bwd_z", "lse");
+  check_scale_f32(scale_ce, logits, "ce_vp_bwd_z", "scale_ce");
+  check_scale_f32(scale_z, logits, "ce_vp_bwd_z", "scale_z");
+  return ce_vp_bwd_impl<true>(logits, targets, lse, scale_ce.data_ptr<float>(),
+                              scale_z.data_ptr<float>(), v0, ignore_index);
 }

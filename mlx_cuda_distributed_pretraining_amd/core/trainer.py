@@ -29,7 +29,7 @@ import torch
 from ..data import DataManager, TokenizerManager
 from ..models.llama import Model, ModelArgs
 from ..ops.attention import document_bounds
-from ..ops.cross_entropy import fused_cross_entropy
+from ..ops.cross_entropy import cross_entropy_with_z, fused_cross_entropy
 from ..optim.enhanced import clip_by_global_norm, global_grad_norm
 from ..optim.flat_fused import FusedFlatAdamW
 from ..optim.manager import OptimizationManager
@@ -219,6 +219,15 @@ class Trainer:
                 "data.preprocessing.document_mask is not supported together with "
                 "system.sequence_parallel: the combination is untested; turn one of them off"
             )
+        # auxiliary z-loss (ops/cross_entropy.py): training forwards optimise
+        # ce + z_loss_coef * mean(lse^2); 0 keeps the plain cross-entropy calls
+        self.z_loss_coef = float(
+            (self.config.training.hyperparameters or {}).get("z_loss_coef", 0.0) or 0.0)
+        if not self.z_loss_coef >= 0.0:
+            raise ValueError(
+                f"training.hyperparameters.z_loss_coef must be >= 0, got {self.z_loss_coef}")
+        self.last_z_loss = None  # device scalar: the last step's mean lse^2
+        self._z_micro = None
         self.logger.log_model_summary(self.model)
 
     def setup_training(self) -> None:
@@ -322,6 +331,11 @@ class Trainer:
                 if p.grad is not None:
                     p.grad.mul_(scale)
 
+    def _add_z_loss(self, ce: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+        """ce + z_loss_coef * z; keeps the raw z of this forward for train_step"""
+        self._z_micro = z.detach()
+        return ce + self.z_loss_coef * z
+
     def compute_loss(self, inputs: torch.Tensor, targets: torch.Tensor):
         mpe = self.model_args.max_position_embeddings
         if mpe and inputs.shape[1] > mpe:
@@ -340,17 +354,28 @@ class Trainer:
             logits = self.model(inputs, doc_start=doc_start, doc_end=doc_end)
         else:
             logits = self.model(inputs)
+        # z-loss only in training forwards: validation stays pure CE, so
+        # val_loss and val_ppl compare across runs
+        with_z = self.z_loss_coef > 0 and self.model.training
         vp0 = getattr(self.model, "_vp_vocab0", -1)
         if vp0 >= 0 and self.model.training:
             # vocab-parallel CE over the sharded lm head (parallel/tp.py):
             # the full [N, V] logits replica never materializes
             from ..parallel.tp import vocab_parallel_cross_entropy
 
-            loss, ntok = vocab_parallel_cross_entropy(
-                logits.reshape(-1, logits.shape[-1]),
-                targets.reshape(-1), vp0,
-                ignore_index=self.tokenizer.PAD_TOKEN,
-            )
+            if with_z:
+                ce, z, ntok = vocab_parallel_cross_entropy(
+                    logits.reshape(-1, logits.shape[-1]),
+                    targets.reshape(-1), vp0,
+                    ignore_index=self.tokenizer.PAD_TOKEN, with_z=True,
+                )
+                loss = self._add_z_loss(ce, z)
+            else:
+                loss, ntok = vocab_parallel_cross_entropy(
+                    logits.reshape(-1, logits.shape[-1]),
+                    targets.reshape(-1), vp0,
+                    ignore_index=self.tokenizer.PAD_TOKEN,
+                )
             aux = getattr(self.model, "aux_loss", None)
             if aux is not None:
                 loss = loss + self.model_args.router_aux_loss_coef * aux
@@ -363,11 +388,20 @@ class Trainer:
 
             s_loc = logits.shape[1]
             tgt = targets[:, self.tp_rank * s_loc:(self.tp_rank + 1) * s_loc]
-            loss_l, ntok_l = fused_cross_entropy(
-                logits.reshape(-1, logits.shape[-1]),
-                tgt.reshape(-1),
-                ignore_index=self.tokenizer.PAD_TOKEN,
-            )
+            if with_z:
+                loss_l, z_l, ntok_l = cross_entropy_with_z(
+                    logits.reshape(-1, logits.shape[-1]),
+                    tgt.reshape(-1),
+                    ignore_index=self.tokenizer.PAD_TOKEN,
+                )
+                # the shard-local mean lse^2, re-weighted like the CE below
+                z_sum = reduce_from_tp((z_l * ntok_l.float()).unsqueeze(0)).squeeze(0)
+            else:
+                loss_l, ntok_l = fused_cross_entropy(
+                    logits.reshape(-1, logits.shape[-1]),
+                    tgt.reshape(-1),
+                    ignore_index=self.tokenizer.PAD_TOKEN,
+                )
             loss_sum = reduce_from_tp((loss_l * ntok_l.float()).unsqueeze(0)).squeeze(0)
             ntok_g = ntok_l.float().clone()
             if is_distributed():
@@ -375,17 +409,27 @@ class Trainer:
 
                 dist.all_reduce(ntok_g, group=self.tp_pg)  # THIS replica's tokens
             loss = loss_sum / ntok_g
+            if with_z:
+                loss = self._add_z_loss(loss, z_sum / ntok_g)
             # MoE under SP: aux is computed on the gathered tokens
             # (identical per rank, pre-divided by ep_world — parallel/tp.py)
             aux = getattr(self.model, "aux_loss", None)
             if aux is not None and self.model.training:
                 loss = loss + self.model_args.router_aux_loss_coef * aux
             return loss, ntok_g.long()
-        loss, ntok = fused_cross_entropy(
-            logits.reshape(-1, logits.shape[-1]),
-            targets.reshape(-1),
-            ignore_index=self.tokenizer.PAD_TOKEN,
-        )
+        if with_z:
+            ce, z, ntok = cross_entropy_with_z(
+                logits.reshape(-1, logits.shape[-1]),
+                targets.reshape(-1),
+                ignore_index=self.tokenizer.PAD_TOKEN,
+            )
+            loss = self._add_z_loss(ce, z)
+        else:
+            loss, ntok = fused_cross_entropy(
+                logits.reshape(-1, logits.shape[-1]),
+                targets.reshape(-1),
+                ignore_index=self.tokenizer.PAD_TOKEN,
+            )
         # MoE: add the router load-balance loss (models/llama.py MoE)
         aux = getattr(self.model, "aux_loss", None)
         if aux is not None and self.model.training:
@@ -428,6 +472,10 @@ class Trainer:
             ld = loss.detach()
             total_loss = ld if total_loss is None else total_loss + ld
             total_tok = ntok if total_tok is None else total_tok + ntok
+            if self.z_loss_coef > 0:
+                total_z = self._z_micro if micro == 0 else total_z + self._z_micro
+        if self.z_loss_coef > 0:
+            self.last_z_loss = total_z / self.grad_accum_steps
         if self.ddp is not None:
             self.ddp.finalize()
         if self.sp:
@@ -482,6 +530,15 @@ class Trainer:
             total = (time.perf_counter() - t_host0) * 1000
             compute_ms, optim_ms = total - t_data * 1000, 0.0
         return f" | data_ms={t_data*1e3:.1f} | compute_ms={compute_ms:.1f} | optim_ms={optim_ms:.1f}"
+
+    def format_z_loss(self) -> str:
+        """The last step's raw z-loss (mean lse^2 over micro-batches and
+        ranks) as a trailing log field; empty when z_loss_coef is 0. Reads the
+        device scalar, so it is called at log time only."""
+        if not self.z_loss_coef > 0 or self.last_z_loss is None:
+            return ""
+        z = all_reduce_scalar(self.last_z_loss.float(), "mean")
+        return f" | z_loss={float(z.item()):.4e}"
 
     # ------------------------------------------------------------------
     @torch.no_grad()
@@ -797,6 +854,7 @@ class Trainer:
                 if cfg.logging.log_gradient_norm and self.flat_space is not None:
                     gnorm = float(self.flat_space.flat_grad.float().norm().item())
                     line += f" | grad_norm={gnorm:.3e}"
+                line += self.format_z_loss()
                 self.logger.log_metrics_line(step + 1, line)
                 self.logger.tb_scalars(step + 1, {"train/loss": loss_v, "train/lr": self.lr_schedule(step)})
                 if cfg.logging.log_memory_usage:

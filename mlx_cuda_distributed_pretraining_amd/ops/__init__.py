@@ -2,7 +2,7 @@ from .rmsnorm import RMSNorm, rms_norm, rms_norm_ref
 from .rope import RopeTable, apply_rope, rope_ref
 from .qk_norm import qk_norm_rope
 from .swiglu import swiglu, swiglu_ref
-from .cross_entropy import fused_cross_entropy, cross_entropy_ref
+from .cross_entropy import cross_entropy_ref, cross_entropy_with_z, fused_cross_entropy
 from .attention import (
     BlockMask,
     attention_ref,
@@ -22,7 +22,7 @@ __all__ = [
     "RopeTable", "apply_rope", "rope_ref",
     "qk_norm_rope",
     "swiglu", "swiglu_ref",
-    "fused_cross_entropy", "cross_entropy_ref",
+    "fused_cross_entropy", "cross_entropy_ref", "cross_entropy_with_z",
     "BlockMask", "attention_ref", "create_block_mask", "document_bounds",
     "flash_attention", "flex_attention",
     "make_sampler", "make_logits_processors", "sample_token",

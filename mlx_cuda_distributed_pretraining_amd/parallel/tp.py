@@ -267,6 +267,26 @@ def vp_embedding(tokens: torch.Tensor, weight: torch.Tensor, v0: int) -> torch.T
     return reduce_from_tp(emb)
 
 
+def _vp_group_lse(logits_local, targets, v0, ignore_index):
+    """The kernel passes and the two group reductions of the vocab-parallel
+    forward: (mask, ntok, lse of the full row, target logit), all [N]."""
+    from ..ops._ext import require_ext
+
+    ext = require_ext()
+    mask = targets != ignore_index
+    ntok = mask.sum()
+    m, tgt_local = ext.ce_vp_stats(logits_local, targets, v0, ignore_index)
+    if _world() > 1:
+        dist.all_reduce(m, op=dist.ReduceOp.MAX, group=_TP_GROUP)
+    se_local = ext.ce_vp_sumexp(logits_local, m)
+    both = torch.stack([se_local, tgt_local])
+    if _world() > 1:
+        dist.all_reduce(both, group=_TP_GROUP)
+    se, tgt = both[0], both[1]
+    lse = m + torch.log(se)
+    return mask, ntok, lse, tgt
+
+
 class _VPCrossEntropyHIP(torch.autograd.Function):
     """Kernel-backed vocab-parallel CE (csrc/cross_entropy.hip ce_vp_*):
     two fused streaming passes over the bf16 shard (local max + target pick,
@@ -277,21 +297,7 @@ class _VPCrossEntropyHIP(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits_local, targets, v0, ignore_index):
-        from ..ops._ext import require_ext
-
-        ext = require_ext()
-        n, v_loc = logits_local.shape
-        mask = targets != ignore_index
-        ntok = mask.sum()
-        m, tgt_local = ext.ce_vp_stats(logits_local, targets, v0, ignore_index)
-        if _world() > 1:
-            dist.all_reduce(m, op=dist.ReduceOp.MAX, group=_TP_GROUP)
-        se_local = ext.ce_vp_sumexp(logits_local, m)
-        both = torch.stack([se_local, tgt_local])
-        if _world() > 1:
-            dist.all_reduce(both, group=_TP_GROUP)
-        se, tgt = both[0], both[1]
-        lse = m + torch.log(se)
+        mask, ntok, lse, tgt = _vp_group_lse(logits_local, targets, v0, ignore_index)
         loss_rows = torch.where(mask, lse - tgt, torch.zeros_like(lse))
         ntok_f = ntok.clamp(min=1).float()
         loss = loss_rows.sum() / ntok_f
@@ -311,18 +317,53 @@ class _VPCrossEntropyHIP(torch.autograd.Function):
         return dl, None, None, None
 
 
+class _VPCrossEntropyZHIP(torch.autograd.Function):
+    """_VPCrossEntropyHIP with the auxiliary z-loss: the same forward passes
+    (z = mean lse^2 comes from the group lse vector they assemble), and one
+    ce_vp_bwd_z launch that takes the upstream gradients of both means."""
+
+    @staticmethod
+    def forward(ctx, logits_local, targets, v0, ignore_index):
+        mask, ntok, lse, tgt = _vp_group_lse(logits_local, targets, v0, ignore_index)
+        zero = torch.zeros_like(lse)
+        ntok_f = ntok.clamp(min=1).float()
+        loss = torch.where(mask, lse - tgt, zero).sum() / ntok_f
+        z = torch.where(mask, lse * lse, zero).sum() / ntok_f
+        ctx.save_for_backward(logits_local, targets, lse, ntok_f)
+        ctx.v0 = v0
+        ctx.ignore_index = ignore_index
+        ctx.mark_non_differentiable(ntok)
+        return loss, z, ntok
+
+    @staticmethod
+    def backward(ctx, gloss, gz, _gntok):
+        from ..ops._ext import require_ext
+
+        logits_local, targets, lse, ntok_f = ctx.saved_tensors
+        scale_ce = (gloss.float() / ntok_f).reshape(1)
+        scale_z = (2.0 * gz.float() / ntok_f).reshape(1)
+        dl = require_ext().ce_vp_bwd_z(logits_local, targets, lse, scale_ce, scale_z,
+                                       ctx.v0, ctx.ignore_index)
+        return dl, None, None, None
+
+
 def vocab_parallel_cross_entropy(logits_local: torch.Tensor, targets: torch.Tensor,
-                                 v0: int, ignore_index: int = -100):
+                                 v0: int, ignore_index: int = -100, with_z: bool = False):
     """Cross entropy over VOCAB-SHARDED logits ([N, V/tp] on each rank,
     this rank owning vocab ids [v0, v0 + V/tp)). Returns (mean_loss, ntok)
     — numerically the full-vocab CE, but the [N, V] logits replica never
-    exists. Composition keeps autograd exact: the logsumexp shift uses a
+    exists. ``with_z=True`` returns (mean_loss, z, ntok), z being the mean of
+    lse^2 over the counted rows (the auxiliary z-loss; ops/cross_entropy.py).
+    Composition keeps autograd exact: the logsumexp shift uses a
     DETACHED group max (lse is shift-invariant), and the cross-rank sums go
     through reduce_from_tp (sum forward / identity backward), so each
     rank's backward produces exactly its shard of the softmax-minus-onehot
     gradient."""
     if (logits_local.is_cuda and logits_local.dtype == torch.bfloat16
             and logits_local.is_contiguous() and logits_local.shape[1] % 8 == 0):
+        if with_z:
+            return _VPCrossEntropyZHIP.apply(logits_local, targets.contiguous(), int(v0),
+                                             int(ignore_index))
         return _VPCrossEntropyHIP.apply(logits_local, targets.contiguous(), int(v0),
                                         int(ignore_index))
     lf = logits_local.float()
@@ -348,6 +389,9 @@ def vocab_parallel_cross_entropy(logits_local: torch.Tensor, targets: torch.Tens
 
     loss_rows = torch.where(mask, lse - tgt, torch.zeros_like(lse))
     loss = loss_rows.sum() / ntok.clamp(min=1).float()
+    if with_z:
+        z = torch.where(mask, lse * lse, torch.zeros_like(lse)).sum() / ntok.clamp(min=1).float()
+        return loss, z, ntok
     return loss, ntok
 
 
