@@ -36,6 +36,20 @@ at::Tensor ce_bwd_z(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::T
                     at::Tensor scale_z, long ignore_index);
 at::Tensor ce_vp_bwd_z(at::Tensor logits, at::Tensor targets, at::Tensor lse,
                        at::Tensor scale_ce, at::Tensor scale_z, long v0, long ignore_index);
+std::vector<at::Tensor> ce_cap_fwd(at::Tensor logits, at::Tensor targets, long ignore_index,
+                                   double cap);
+at::Tensor ce_cap_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Tensor scale_ce,
+                      at::Tensor scale_z, long ignore_index, double cap);
+std::vector<at::Tensor> ce_vp_cap_stats(at::Tensor logits, at::Tensor targets, long v0,
+                                        long ignore_index, double cap);
+at::Tensor ce_vp_cap_sumexp(at::Tensor logits, at::Tensor m_group, double cap);
+at::Tensor ce_vp_cap_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
+                         at::Tensor scale_ce, at::Tensor scale_z, long v0, long ignore_index,
+                         double cap);
+// softcap.hip
+at::Tensor softcap_fwd(at::Tensor x, double cap);
+void softcap_(at::Tensor x, double cap);
+at::Tensor softcap_bwd(at::Tensor dy, at::Tensor y, double cap);
 // optim.hip
 at::Tensor sumsq(at::Tensor g);
 void adamw_step(at::Tensor param, at::Tensor master, at::Tensor grad, at::Tensor m,
@@ -132,6 +146,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_fwd_z", &ce_fwd_z, "cross-entropy + z-loss forward (loss_sum, z_sum, ntok, lse)");
   m.def("ce_bwd_z", &ce_bwd_z, "cross-entropy + z-loss backward (dlogits)");
   m.def("ce_vp_bwd_z", &ce_vp_bwd_z, "vocab-parallel cross-entropy + z-loss backward (dlogits)");
+  m.def("ce_cap_fwd", &ce_cap_fwd,
+        "cross-entropy + z-loss forward of cap * tanh(logits / cap) (loss_sum, z_sum, ntok, lse)");
+  m.def("ce_cap_bwd", &ce_cap_bwd, "backward of ce_cap_fwd (dlogits)");
+  m.def("ce_vp_cap_stats", &ce_vp_cap_stats, "ce_vp_stats of the capped shard (m_local, tgt_local)");
+  m.def("ce_vp_cap_sumexp", &ce_vp_cap_sumexp, "ce_vp_sumexp of the capped shard");
+  m.def("ce_vp_cap_bwd", &ce_vp_cap_bwd, "ce_vp_bwd_z of the capped shard (dlogits)");
+  m.def("softcap_fwd", &softcap_fwd, "y = cap * tanh(x / cap)");
+  m.def("softcap_", &softcap_, "x = cap * tanh(x / cap) in place");
+  m.def("softcap_bwd", &softcap_bwd, "dx = dy * (1 - (y / cap)^2) from the saved output");
   m.def("sumsq", &sumsq, "sum of squares -> f32 scalar");
   m.def("adamw_step", &adamw_step, "fused AdamW over flat buffers");
   m.def("lion_step", &lion_step, "fused Lion over flat buffers");

@@ -29,7 +29,11 @@ import torch
 from ..data import DataManager, TokenizerManager
 from ..models.llama import Model, ModelArgs
 from ..ops.attention import document_bounds
-from ..ops.cross_entropy import cross_entropy_with_z, fused_cross_entropy
+from ..ops.cross_entropy import (
+    cross_entropy_capped,
+    cross_entropy_with_z,
+    fused_cross_entropy,
+)
 from ..optim.enhanced import clip_by_global_norm, global_grad_norm
 from ..optim.flat_fused import FusedFlatAdamW
 from ..optim.manager import OptimizationManager
@@ -351,9 +355,16 @@ class Trainer:
             # validation alike); bounds follow the truncation above
             doc_start, doc_end = document_bounds(
                 inputs, bos_id=self.tokenizer.BOS_TOKEN, eos_id=self.tokenizer.EOS_TOKEN)
-            logits = self.model(inputs, doc_start=doc_start, doc_end=doc_end)
+            fwd_kw = {"doc_start": doc_start, "doc_end": doc_end}
         else:
-            logits = self.model(inputs)
+            fwd_kw = {}
+        # final-logit soft-capping (model.misc.logit_softcap): the model hands
+        # over its raw logits and the capped loss ops cap them in their kernels.
+        # The capped distribution is the model's own, so validation uses it too.
+        cap = getattr(self.model_args, "logit_softcap", None)
+        if cap:
+            fwd_kw["cap_logits"] = False
+        logits = self.model(inputs, **fwd_kw)
         # z-loss only in training forwards: validation stays pure CE, so
         # val_loss and val_ppl compare across runs
         with_z = self.z_loss_coef > 0 and self.model.training
@@ -363,7 +374,15 @@ class Trainer:
             # the full [N, V] logits replica never materializes
             from ..parallel.tp import vocab_parallel_cross_entropy
 
-            if with_z:
+            if cap:
+                loss, z, ntok = vocab_parallel_cross_entropy(
+                    logits.reshape(-1, logits.shape[-1]),
+                    targets.reshape(-1), vp0,
+                    ignore_index=self.tokenizer.PAD_TOKEN, with_z=True, softcap=cap,
+                )
+                if with_z:
+                    loss = self._add_z_loss(loss, z)
+            elif with_z:
                 ce, z, ntok = vocab_parallel_cross_entropy(
                     logits.reshape(-1, logits.shape[-1]),
                     targets.reshape(-1), vp0,
@@ -388,20 +407,27 @@ class Trainer:
 
             s_loc = logits.shape[1]
             tgt = targets[:, self.tp_rank * s_loc:(self.tp_rank + 1) * s_loc]
-            if with_z:
+            if cap:
+                loss_l, z_l, ntok_l = cross_entropy_capped(
+                    logits.reshape(-1, logits.shape[-1]),
+                    tgt.reshape(-1), cap,
+                    ignore_index=self.tokenizer.PAD_TOKEN,
+                )
+            elif with_z:
                 loss_l, z_l, ntok_l = cross_entropy_with_z(
                     logits.reshape(-1, logits.shape[-1]),
                     tgt.reshape(-1),
                     ignore_index=self.tokenizer.PAD_TOKEN,
                 )
-                # the shard-local mean lse^2, re-weighted like the CE below
-                z_sum = reduce_from_tp((z_l * ntok_l.float()).unsqueeze(0)).squeeze(0)
             else:
                 loss_l, ntok_l = fused_cross_entropy(
                     logits.reshape(-1, logits.shape[-1]),
                     tgt.reshape(-1),
                     ignore_index=self.tokenizer.PAD_TOKEN,
                 )
+            if with_z:
+                # the shard-local mean lse^2, re-weighted like the CE below
+                z_sum = reduce_from_tp((z_l * ntok_l.float()).unsqueeze(0)).squeeze(0)
             loss_sum = reduce_from_tp((loss_l * ntok_l.float()).unsqueeze(0)).squeeze(0)
             ntok_g = ntok_l.float().clone()
             if is_distributed():
@@ -417,7 +443,15 @@ class Trainer:
             if aux is not None and self.model.training:
                 loss = loss + self.model_args.router_aux_loss_coef * aux
             return loss, ntok_g.long()
-        if with_z:
+        if cap:
+            loss, z, ntok = cross_entropy_capped(
+                logits.reshape(-1, logits.shape[-1]),
+                targets.reshape(-1), cap,
+                ignore_index=self.tokenizer.PAD_TOKEN,
+            )
+            if with_z:
+                loss = self._add_z_loss(loss, z)
+        elif with_z:
             ce, z, ntok = cross_entropy_with_z(
                 logits.reshape(-1, logits.shape[-1]),
                 targets.reshape(-1),

@@ -33,6 +33,7 @@ from ..ops.gemv import FastLinear, linear_fast
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
 from ..parallel.tp import copy_to_tp, gather_sp, reduce_from_tp, scatter_sp, tp_group
 from ..ops.qk_norm import qk_norm_rope
+from ..ops.softcap import softcap, softcap_
 from ..ops.rope import RopeTable, apply_rope
 from ..ops.swiglu import swiglu
 
@@ -55,6 +56,9 @@ class ModelArgs:
     mlp_bias: bool = False
     tie_word_embeddings: bool = True
     logit_scale: Optional[float] = None
+    # final-logit soft-capping, logits = c * tanh(logits / c) after logit_scale
+    # (Gemma-2; ops/softcap.py). None or 0 = off.
+    logit_softcap: Optional[float] = None
     attention_type: str = "flash"  # flash | flex | simple
     attention_window: Optional[int] = None  # sliding-window size (flex)
     attention_prefix_len: Optional[int] = None  # prefix-LM split (flex)
@@ -75,6 +79,12 @@ class ModelArgs:
             self.num_kv_heads = self.num_heads
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_heads
+        if self.logit_softcap is not None:
+            c = float(self.logit_softcap)
+            if not (math.isfinite(c) and c >= 0.0):
+                raise ValueError(
+                    f"model.misc.logit_softcap must be finite and >= 0 (0 = off), got {c}")
+            self.logit_softcap = c or None
 
     @classmethod
     def from_config(cls, model_cfg: Any, vocab_size: int) -> "ModelArgs":
@@ -100,6 +110,7 @@ class ModelArgs:
             mlp_bias=bool(misc.get("mlp_bias", False)),
             tie_word_embeddings=bool(misc.get("tie_word_embeddings", True)),
             logit_scale=misc.get("logit_scale"),
+            logit_softcap=misc.get("logit_softcap"),
             fp8=bool(misc.get("fp8", False)),
             router_aux_loss_coef=float(misc.get("router_aux_loss_coef", 0.01)),
             attention_type=str(attn.get("type", "flash")),
@@ -572,11 +583,18 @@ class Model(nn.Module):
         self, tokens: torch.Tensor, cache: Optional[List[KVCache]] = None,
         doc_start: Optional[torch.Tensor] = None,
         doc_end: Optional[torch.Tensor] = None,
+        cap_logits: bool = True,
     ) -> torch.Tensor:
         """``doc_start`` / ``doc_end`` (int32 [B, S], ops.attention.
         document_bounds): packed-sequence document mask for every layer —
         each token attends inside its own document only. Full-sequence
-        forwards only (no cache); not combinable with set_flex_mask."""
+        forwards only (no cache); not combinable with set_flex_mask.
+
+        With ``args.logit_softcap`` = c the returned logits are
+        c * tanh(logits / c), on every path; ``cap_logits=False`` returns
+        them uncapped, for a caller that caps inside its loss (the trainer,
+        ops.cross_entropy_capped)."""
+        cap = self.args.logit_softcap if cap_logits else None
         if doc_start is None and doc_end is not None:
             raise ValueError("doc_end needs doc_start")
         if doc_start is not None and cache is not None:
@@ -650,6 +668,8 @@ class Model(nn.Module):
                 logits = self.output(x)
             if self.args.logit_scale:
                 logits = logits * self.args.logit_scale
+            if cap:
+                logits = softcap(logits, cap)
             return logits
         for i, layer in enumerate(self.layers):
             x = layer(x, cache[i] if cache is not None else None)
@@ -672,6 +692,8 @@ class Model(nn.Module):
             ).view(x.shape[0], 1, -1)
             if self.args.logit_scale:
                 logits = logits * self.args.logit_scale
+            if cap:
+                softcap_(logits, cap)  # in place: the captured graph allocates nothing here
             return logits
         x = self.norm(x)
         if self.args.tie_word_embeddings:
@@ -680,6 +702,8 @@ class Model(nn.Module):
             logits = self.output(x)
         if self.args.logit_scale:
             logits = logits * self.args.logit_scale
+        if cap:
+            logits = softcap(logits, cap)
         return logits
 
     @property

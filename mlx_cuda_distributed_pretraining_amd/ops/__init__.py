@@ -2,7 +2,13 @@ from .rmsnorm import RMSNorm, rms_norm, rms_norm_ref
 from .rope import RopeTable, apply_rope, rope_ref
 from .qk_norm import qk_norm_rope
 from .swiglu import swiglu, swiglu_ref
-from .cross_entropy import cross_entropy_ref, cross_entropy_with_z, fused_cross_entropy
+from .cross_entropy import (
+    cross_entropy_capped,
+    cross_entropy_ref,
+    cross_entropy_with_z,
+    fused_cross_entropy,
+)
+from .softcap import softcap, softcap_
 from .attention import (
     BlockMask,
     attention_ref,
@@ -23,6 +29,7 @@ __all__ = [
     "qk_norm_rope",
     "swiglu", "swiglu_ref",
     "fused_cross_entropy", "cross_entropy_ref", "cross_entropy_with_z",
+    "cross_entropy_capped", "softcap", "softcap_",
     "BlockMask", "attention_ref", "create_block_mask", "document_bounds",
     "flash_attention", "flex_attention",
     "make_sampler", "make_logits_processors", "sample_token",

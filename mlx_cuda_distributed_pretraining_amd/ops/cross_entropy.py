@@ -17,6 +17,10 @@ one backward kernel writes
 so z-loss costs one multiply-add per element and no further pass over the
 logits (``ce_fwd_z`` / ``ce_bwd_z``; the plain ``ce_fwd`` / ``ce_bwd`` stay as
 they were and ``fused_cross_entropy`` still runs them).
+
+``cross_entropy_capped`` is that loss of the soft-capped logits
+``cap * tanh(logits / cap)``, capped inside the kernels (``ce_cap_fwd`` /
+``ce_cap_bwd``).
 """
 from __future__ import annotations
 
@@ -25,6 +29,7 @@ from typing import Tuple
 import torch
 
 from ._ext import get_ext, use_hip
+from .softcap import check_cap
 
 
 def cross_entropy_ref(
@@ -143,3 +148,52 @@ def cross_entropy_with_z(
     ce = ((lse - picked) * mask).sum() / denom
     z = (lse * lse * mask).sum() / denom
     return ce, z, ntok
+
+
+class _FusedCECappedFn(torch.autograd.Function):
+    """_FusedCEWithZFn over the capped kernels: ce_cap_fwd / ce_cap_bwd cap
+    every logit in registers, so neither the capped [N, V] tensor nor a saved
+    copy for tanh's backward exists."""
+
+    @staticmethod
+    def forward(ctx, logits: torch.Tensor, targets: torch.Tensor, cap: float,
+                ignore_index: int):
+        ext = get_ext()
+        loss_sum, z_sum, ntok, lse = ext.ce_cap_fwd(
+            logits.contiguous(), targets.contiguous(), ignore_index, cap)
+        ctx.save_for_backward(logits, targets, lse, ntok)
+        ctx.ignore_index = ignore_index
+        ctx.cap = cap
+        ctx.mark_non_differentiable(ntok)
+        ntok_f = ntok.clamp(min=1)
+        return loss_sum / ntok_f, z_sum / ntok_f, ntok
+
+    @staticmethod
+    def backward(ctx, g_ce, g_z, _dntok):
+        logits, targets, lse, ntok = ctx.saved_tensors
+        ntok_f = ntok.clamp(min=1).float()
+        scale_ce = (g_ce.float() / ntok_f).reshape(1)
+        scale_z = (2.0 * g_z.float() / ntok_f).reshape(1)
+        dlogits = get_ext().ce_cap_bwd(
+            logits.contiguous(), targets.contiguous(), lse, scale_ce, scale_z,
+            ctx.ignore_index, ctx.cap)
+        return dlogits, None, None, None
+
+
+def cross_entropy_capped(
+    logits: torch.Tensor, targets: torch.Tensor, cap: float, ignore_index: int = -100
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``cross_entropy_with_z`` of the soft-capped logits
+    ``t = cap * tanh(logits / cap)`` (final-logit soft-capping, Gemma-2):
+    (ce_mean, z_mean, ntok) with lse, and so z, those of the capped rows. The
+    gradient reaches the raw logits: ``(p * (a + b * lse) - a * onehot) *
+    (1 - (t / cap)^2)`` with a and b as in ``cross_entropy_with_z``. The HIP
+    path (same rule as ``fused_cross_entropy``) caps inside ``ce_cap_fwd`` /
+    ``ce_cap_bwd`` and moves the bytes of the plain loss; elsewhere the torch
+    composition runs on ``softcap(logits)``, in fp64 for fp64 logits and in
+    fp32 otherwise."""
+    cap = check_cap(cap)
+    if use_hip(logits) and logits.shape[-1] % 8 == 0:  # kernel needs V%8==0
+        return _FusedCECappedFn.apply(logits, targets, cap, ignore_index)
+    lf = logits if logits.dtype == torch.float64 else logits.float()
+    return cross_entropy_with_z(cap * torch.tanh(lf / cap), targets, ignore_index)

@@ -267,18 +267,25 @@ def vp_embedding(tokens: torch.Tensor, weight: torch.Tensor, v0: int) -> torch.T
     return reduce_from_tp(emb)
 
 
-def _vp_group_lse(logits_local, targets, v0, ignore_index):
+def _vp_group_lse(logits_local, targets, v0, ignore_index, cap=0.0):
     """The kernel passes and the two group reductions of the vocab-parallel
-    forward: (mask, ntok, lse of the full row, target logit), all [N]."""
+    forward: (mask, ntok, lse of the full row, target logit), all [N]. With a
+    cap, all of the soft-capped row (ce_vp_cap_*)."""
     from ..ops._ext import require_ext
 
     ext = require_ext()
     mask = targets != ignore_index
     ntok = mask.sum()
-    m, tgt_local = ext.ce_vp_stats(logits_local, targets, v0, ignore_index)
+    if cap:
+        m, tgt_local = ext.ce_vp_cap_stats(logits_local, targets, v0, ignore_index, cap)
+    else:
+        m, tgt_local = ext.ce_vp_stats(logits_local, targets, v0, ignore_index)
     if _world() > 1:
         dist.all_reduce(m, op=dist.ReduceOp.MAX, group=_TP_GROUP)
-    se_local = ext.ce_vp_sumexp(logits_local, m)
+    if cap:
+        se_local = ext.ce_vp_cap_sumexp(logits_local, m, cap)
+    else:
+        se_local = ext.ce_vp_sumexp(logits_local, m)
     both = torch.stack([se_local, tgt_local])
     if _world() > 1:
         dist.all_reduce(both, group=_TP_GROUP)
@@ -347,26 +354,72 @@ class _VPCrossEntropyZHIP(torch.autograd.Function):
         return dl, None, None, None
 
 
+class _VPCrossEntropyCapHIP(torch.autograd.Function):
+    """_VPCrossEntropyZHIP of the soft-capped logits cap * tanh(l / cap): the
+    ce_vp_cap_* kernels cap the shard in registers. There is one capped
+    variant, so z is always computed (a zero upstream gradient of z leaves
+    the pure capped CE)."""
+
+    @staticmethod
+    def forward(ctx, logits_local, targets, v0, ignore_index, cap):
+        mask, ntok, lse, tgt = _vp_group_lse(logits_local, targets, v0, ignore_index, cap)
+        zero = torch.zeros_like(lse)
+        ntok_f = ntok.clamp(min=1).float()
+        loss = torch.where(mask, lse - tgt, zero).sum() / ntok_f
+        z = torch.where(mask, lse * lse, zero).sum() / ntok_f
+        ctx.save_for_backward(logits_local, targets, lse, ntok_f)
+        ctx.v0 = v0
+        ctx.ignore_index = ignore_index
+        ctx.cap = cap
+        ctx.mark_non_differentiable(ntok)
+        return loss, z, ntok
+
+    @staticmethod
+    def backward(ctx, gloss, gz, _gntok):
+        from ..ops._ext import require_ext
+
+        logits_local, targets, lse, ntok_f = ctx.saved_tensors
+        scale_ce = (gloss.float() / ntok_f).reshape(1)
+        scale_z = (2.0 * gz.float() / ntok_f).reshape(1)
+        dl = require_ext().ce_vp_cap_bwd(logits_local, targets, lse, scale_ce, scale_z,
+                                         ctx.v0, ctx.ignore_index, ctx.cap)
+        return dl, None, None, None, None
+
+
 def vocab_parallel_cross_entropy(logits_local: torch.Tensor, targets: torch.Tensor,
-                                 v0: int, ignore_index: int = -100, with_z: bool = False):
+                                 v0: int, ignore_index: int = -100, with_z: bool = False,
+                                 softcap: float = 0.0):
     """Cross entropy over VOCAB-SHARDED logits ([N, V/tp] on each rank,
     this rank owning vocab ids [v0, v0 + V/tp)). Returns (mean_loss, ntok)
     — numerically the full-vocab CE, but the [N, V] logits replica never
     exists. ``with_z=True`` returns (mean_loss, z, ntok), z being the mean of
     lse^2 over the counted rows (the auxiliary z-loss; ops/cross_entropy.py).
+    ``softcap = c > 0`` takes the loss of the soft-capped logits
+    c * tanh(l / c) (ops.cross_entropy_capped): in the ce_vp_cap_* kernels on
+    the HIP path, on the capped shard in the torch composition.
     Composition keeps autograd exact: the logsumexp shift uses a
     DETACHED group max (lse is shift-invariant), and the cross-rank sums go
     through reduce_from_tp (sum forward / identity backward), so each
     rank's backward produces exactly its shard of the softmax-minus-onehot
     gradient."""
+    if softcap:
+        from ..ops.softcap import check_cap
+
+        softcap = check_cap(softcap)
     if (logits_local.is_cuda and logits_local.dtype == torch.bfloat16
             and logits_local.is_contiguous() and logits_local.shape[1] % 8 == 0):
+        if softcap:
+            loss, z, ntok = _VPCrossEntropyCapHIP.apply(
+                logits_local, targets.contiguous(), int(v0), int(ignore_index), softcap)
+            return (loss, z, ntok) if with_z else (loss, ntok)
         if with_z:
             return _VPCrossEntropyZHIP.apply(logits_local, targets.contiguous(), int(v0),
                                              int(ignore_index))
         return _VPCrossEntropyHIP.apply(logits_local, targets.contiguous(), int(v0),
                                         int(ignore_index))
     lf = logits_local.float()
+    if softcap:
+        lf = softcap * torch.tanh(lf / softcap)
     n, v_loc = lf.shape
     mask = targets != ignore_index
     ntok = mask.sum()

@@ -78,7 +78,19 @@ def fused_to_hf_state(state: Dict[str, torch.Tensor], args: ModelArgs) -> Dict[s
     return out
 
 
+def check_exportable(args: ModelArgs) -> None:
+    """The llama / qwen3 layouts written here have no final-logit soft-cap: a
+    loader would decode a capped model from its raw logits, i.e. differently."""
+    if getattr(args, "logit_softcap", None):
+        raise NotImplementedError(
+            f"convert_to_mlx_lm: model.misc.logit_softcap = {args.logit_softcap} has no "
+            "equivalent in the llama / qwen3 layouts this tool writes; the exported model "
+            "would decode without the cap (a Gemma-2 layout is a ROADMAP item)"
+        )
+
+
 def hf_config_from(config: Config, args: ModelArgs) -> Dict:
+    check_exportable(args)
     # Llama + per-head QK RMSNorm before RoPE + explicit head_dim is the Qwen3
     # architecture; without QK-norm the export stays plain Llama.
     qk_norm = getattr(args, "qk_norm", False)
@@ -129,6 +141,7 @@ def convert_run(run_dir: str | Path, out_path: str | Path, checkpoint: str = "fi
         raise NotImplementedError(
             "convert_to_mlx_lm: MoE runs have no HF-Llama equivalent layout"
         )
+    check_exportable(args)  # before any file is written
 
     model_path, _opt, _state = CheckpointManager.get_checkpoint_paths(
         str(run_dir / "checkpoints" / f"step_{checkpoint}")
