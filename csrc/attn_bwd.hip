@@ -119,8 +119,21 @@ __device__ __forceinline__ void doc_range_for_kv(
   dend_wmax = de[min(kv0u + 31, Skv - 1)];
 }
 
+// Attention-logit soft-capping (softcap.h), the one per-element body of the
+// capped dQ loop and the capped bwd_p_ds_tile: p comes from the capped score
+// t, p = 2^(t * log2e - lse2) with the forward's lse of the capped scores.
+// dS = p * (dP - Drow) is then the gradient with respect to t, and the chain
+// rule puts dfac = d t / d x = 1 - (t / c)^2 in front of `scale`.
+__device__ __forceinline__ float cap_p(float acc, float lse2, const AttnCap& cp, float& dfac) {
+  const float t2 = softcap_val(acc, cp.c2, cp.sic);
+  dfac = softcap_dfac(t2, cp.inv_c2);
+  return __builtin_amdgcn_exp2f(t2 - lse2);
+}
+
 // ---------------- dQ kernel (block per q-tile of QPB rows) ----------------
-template <int D, int MOD>
+// CAP: the capped instantiations (MOD_NONE / MOD_CAUSAL / MOD_SLIDING_WINDOW)
+// take one trailing AttnCap argument; the others do not have it at all.
+template <int D, int MOD, bool CAP = false, typename... Cap>
 __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dq_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
@@ -138,7 +151,11 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dq_kernel(
     const int* __restrict__ mb_range = nullptr,
     const __hip_bfloat16* __restrict__ bias = nullptr,
     // MOD_DOCUMENT only: doc_start int32 [B,Sq] (see attn_fwd.hip)
-    const int* __restrict__ doc_start = nullptr) {
+    const int* __restrict__ doc_start = nullptr, Cap... cap) {
+  static_assert(sizeof...(Cap) == (CAP ? 1 : 0), "CAP takes (AttnCap cap)");
+  static_assert(!CAP || MOD == MOD_NONE || MOD == MOD_CAUSAL || MOD == MOD_SLIDING_WINDOW,
+                "capped instantiations: none, causal, sliding window");
+  [[maybe_unused]] const AttnCap cp = attn_cap_arg(cap...);
   // waves per block (NW=4 measured 2.4x slower at D=128: 139 vs 331 TF); the
   // blockmask tensors are laid out for the resulting 256-row q blocks
   constexpr int NW = 8;
@@ -318,10 +335,16 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dq_kernel(
 
       // S^T = mfma(K, Q); dP^T = mfma(V, dO) — both (r=k_local, c=q_local)
       f32x16 st = {}, dpt = {};
+      // capped, D=128: opaque copies of the lane id (here and before the dQ
+      // accumulate), as in the merged dK+dV kernel. The swizzled LDS offsets
+      // are then re-formed per sub-tile instead of living across the cap
+      // arithmetic: 226 VGPRs and no scratch, against 256 + 32 B without.
+      int lane_s = lane;
+      if constexpr (CAP && D == 128) asm volatile("" : "+v"(lane_s));
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int dblk = 0; dblk < DBLK; ++dblk) {
-        const int off = rm_swz<D>(lq, dblk * 16 + hi * 8);
+        const int off = rm_swz<D>(lane_s & 31, dblk * 16 + (lane_s >> 5) * 8);
         Bf16x8U kf, vf;
         *reinterpret_cast<uint4*>(kf.s) = *reinterpret_cast<const uint4*>(k_lds + off);
         *reinterpret_cast<uint4*>(vf.s) = *reinterpret_cast<const uint4*>(v_lds + off);
@@ -352,7 +375,28 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dq_kernel(
       }
 
       float ds[16];
-      if (full) {
+      if constexpr (CAP) {
+        if (full) {
+#pragma unroll
+          for (int reg = 0; reg < 16; ++reg) {
+            float dfac;
+            const float p = cap_p(st[reg], Lq2, cp, dfac);
+            ds[reg] = p * (dpt[reg] - Dq) * dfac * scale;
+          }
+        } else {
+#pragma unroll
+          for (int reg = 0; reg < 16; ++reg) {
+            const int k_pos = kvh + acc_row(reg, hi);
+            const bool keep = q_valid && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
+            // the mask rides on the lse operand (p = 2^-inf = 0, every other
+            // factor is finite): a select on ds instead keeps st and dpt of
+            // both sub-tiles live and spills at D=128
+            float dfac;
+            const float p = cap_p(st[reg], keep ? Lq2 : INFINITY, cp, dfac);
+            ds[reg] = p * (dpt[reg] - Dq) * dfac * scale;
+          }
+        }
+      } else if (full) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
           const float p = __builtin_amdgcn_exp2f(st[reg] * scale2 - Lq2);
@@ -399,6 +443,8 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dq_kernel(
 
       bf16x8 da0, da1;
       acc_to_afrag(ds, da0, da1);  // -> dS[32q x 16k] A-fragments
+      int lane_t = lane;
+      if constexpr (CAP && D == 128) asm volatile("" : "+v"(lane_t));
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int dc = 0; dc < DCOL; ++dc) {
@@ -408,7 +454,7 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dq_kernel(
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           // B = K[16k x 32d]: tr_read from the row-major K image
-          bf16x8 kb = tr16_frag<D>(k_lds, ks * 16 + hi * 8, dc * 32, lane);
+          bf16x8 kb = tr16_frag<D>(k_lds, ks * 16 + (lane_t >> 5) * 8, dc * 32, lane_t);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks == 0 ? da0 : da1, kb, acc, 0, 0, 0);
         }
 #pragma unroll
@@ -454,7 +500,9 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dq_kernel(
 //   full           : wave-uniform, every element of the tile is kept
 //   pv  <- p                        (WANT_P)
 //   dsv <- p * (dP - Drow) * scale  (WANT_DS)
-template <int MOD, bool WANT_P, bool WANT_DS>
+// CAP (one trailing AttnCap argument): p and dS of the capped scores (cap_p)
+//   dsv <- p * (dP - Drow) * (1 - (t / c)^2) * scale
+template <int MOD, bool WANT_P, bool WANT_DS, bool CAP = false, typename... Cap>
 __device__ __forceinline__ void bwd_p_ds_tile(
     const f32x16& s_acc, const f32x16& dp_acc, const float* Ls, const float* Ds,
     bool full, int hi, int q0, int q_off, int krow, bool k_valid, int Sq, int Skv,
@@ -462,8 +510,33 @@ __device__ __forceinline__ void bwd_p_ds_tile(
     // MOD_DOCUMENT: this lane's doc end; MOD_BLOCKMASK: bits / bias planes and
     // the (b, q head) plane index
     int dend, const unsigned char* mb_bits, const __hip_bfloat16* bias, long bh, int kvb8,
-    float (&pv)[16], float (&dsv)[16]) {
-  if (full) {
+    float (&pv)[16], float (&dsv)[16], Cap... cap) {
+  static_assert(sizeof...(Cap) == (CAP ? 1 : 0), "CAP takes (AttnCap cap)");
+  if constexpr (CAP) {
+    const AttnCap cp = attn_cap_arg(cap...);
+    if (full) {
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int qr = acc_row(reg, hi);
+        float dfac;
+        const float p = cap_p(s_acc[reg], Ls[qr], cp, dfac);
+        if constexpr (WANT_P) pv[reg] = p;
+        if constexpr (WANT_DS) dsv[reg] = p * (dp_acc[reg] - Ds[qr]) * dfac * scale;
+      }
+    } else {
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int qr = acc_row(reg, hi);
+        const int q_r = q0 + qr;
+        const bool keep =
+            k_valid && q_r < Sq && attn_keep<MOD>(q_r + q_off, krow, Skv, modarg);
+        float dfac;
+        const float p = cap_p(s_acc[reg], Ls[qr], cp, dfac);
+        if constexpr (WANT_P) pv[reg] = keep ? p : 0.f;
+        if constexpr (WANT_DS) dsv[reg] = keep ? p * (dp_acc[reg] - Ds[qr]) * dfac * scale : 0.f;
+      }
+    }
+  } else if (full) {
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
       const int qr = acc_row(reg, hi);
@@ -512,7 +585,8 @@ __device__ __forceinline__ void bwd_p_ds_tile(
 // The split pair: the path for D=64, the blockmask entry point and
 // MCDP_ATTN_BWD_SPLIT=1; everything else runs the merged kernel below.
 // WANT_DK: true -> dK (needs dP: V frags + dO rm); false -> dV (needs dO^T).
-template <int D, int MOD, bool WANT_DK>
+// CAP: capped scores (bwd_p_ds_tile), one trailing AttnCap argument.
+template <int D, int MOD, bool WANT_DK, bool CAP = false, typename... Cap>
 __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dkv_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
@@ -529,7 +603,10 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dkv_kernel(
     const __hip_bfloat16* __restrict__ bias = nullptr,
     // MOD_DOCUMENT only: doc_end int32 [B,Skv], one past the last position of
     // each row's document (non-decreasing along s; same for every head)
-    const int* __restrict__ doc_end = nullptr) {
+    const int* __restrict__ doc_end = nullptr, Cap... cap) {
+  static_assert(sizeof...(Cap) == (CAP ? 1 : 0), "CAP takes (AttnCap cap)");
+  static_assert(!CAP || MOD == MOD_NONE || MOD == MOD_CAUSAL || MOD == MOD_SLIDING_WINDOW,
+                "capped instantiations: none, causal, sliding window");
   constexpr int NW = 8;  // waves per block (NW=4 measured 2.4x slower at D=128)
   constexpr int TPB = NW * WAVE;
   constexpr int KPB = 32 * NW;
@@ -780,10 +857,11 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dkv_kernel(
 
           // dS (dK) or P (dV) of the tile; the other array stays unused
           float pv[16], pv_unused[16];
-          bwd_p_ds_tile<MOD, !WANT_DK, WANT_DK>(
+          bwd_p_ds_tile<MOD, !WANT_DK, WANT_DK, CAP>(
               s_acc, dp_acc, &stats_lds[buf][0][s * 32], &stats_lds[buf][1][s * 32], full, hi,
               q0, q_off, krow, k_valid, Sq, Skv, modarg, scale, scale2, slope2, dend, mb_bits,
-              bias, (long)b * Hq + hq_, kvb8, WANT_DK ? pv_unused : pv, WANT_DK ? pv : pv_unused);
+              bias, (long)b * Hq + hq_, kvb8, WANT_DK ? pv_unused : pv, WANT_DK ? pv : pv_unused,
+              cap...);
 
           // transform: acc holds M[r=q][c=k]; A-frags of M^T = dS^T (dK) / P^T (dV)
           bf16x8 a0, a1;
@@ -857,7 +935,8 @@ store:
 //   Q/dO tiles 2 x 16 KB + K image 8 x 7 KB + V image 8 x 8 KB + stats 512 B.
 // p and dS come from bwd_p_ds_tile and each accumulator sees its MFMAs in
 // the split kernels' order, so dK and dV are bit-identical to theirs.
-template <int D, int MOD>
+// CAP: capped scores (bwd_p_ds_tile), one trailing AttnCap argument.
+template <int D, int MOD, bool CAP = false, typename... Cap>
 __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dkdv_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
@@ -867,7 +946,10 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dkdv_kernel(
     int B, int Sq, int Skv, int Hq, int Hkv, float scale, int modarg,
     long q_rs, long k_rs, long v_rs, long do_rs, long dk_rs, long dv_rs,
     // MOD_DOCUMENT only: doc_end int32 [B,Skv], as in the split kernels
-    const int* __restrict__ doc_end = nullptr) {
+    const int* __restrict__ doc_end = nullptr, Cap... cap) {
+  static_assert(sizeof...(Cap) == (CAP ? 1 : 0), "CAP takes (AttnCap cap)");
+  static_assert(!CAP || MOD == MOD_NONE || MOD == MOD_CAUSAL || MOD == MOD_SLIDING_WINDOW,
+                "capped instantiations: none, causal, sliding window");
   static_assert(D == 128, "merged dK+dV kernel is built for D=128");
   static_assert(MOD != MOD_BLOCKMASK, "blockmask stays on the split kernels");
   constexpr int NW = 8;
@@ -1039,10 +1121,10 @@ __global__ __launch_bounds__(8 * WAVE) void attn_bwd_dkdv_kernel(
       }
 
       float pv[16], dsv[16];
-      bwd_p_ds_tile<MOD, true, true>(
+      bwd_p_ds_tile<MOD, true, true, CAP>(
           s_acc, dp_acc, &stats_lds[buf][0][0], &stats_lds[buf][1][0], full, hi, q0, q_off,
           krow, k_valid, Sq, Skv, modarg, scale, scale2, slope2, dend, nullptr, nullptr, 0, 0,
-          pv, dsv);
+          pv, dsv, cap...);
 
       // dV += P^T . dO first: the packed P fragments die before dK starts
       int lane_t = lane;
@@ -1137,7 +1219,9 @@ store:
 
 // The one backward launch sequence: Drow, dQ, then dK and dV. 8 waves per
 // block of 256 q rows (dQ) / 256 kv rows (dK, dV).
-template <int MOD>
+// CAP: the capped instantiations, with make_attn_cap(a.cap, a.scale) as their
+// trailing argument; the others are launched exactly as before.
+template <int MOD, bool CAP = false>
 void run_bwd(const AttnArgs& a, const at::Tensor& q, bool force_split) {
   auto drow_t = at::empty({(long)a.B * a.Sq * a.Hq}, q.options().dtype(at::kFloat));
   const float* drow = drow_t.data_ptr<float>();
@@ -1152,27 +1236,38 @@ void run_bwd(const AttnArgs& a, const at::Tensor& q, bool force_split) {
   constexpr int BLK = 8 * 32;
   const dim3 gq(cdiv(a.Sq, BLK), a.Hq, a.B), gkv(cdiv(a.Skv, BLK), a.Hkv, a.B), block(8 * WAVE);
   const bool split = force_split || bwd_split();
+  // launch(cap...) with the cap argument when CAP, with nothing otherwise
+  auto with_cap = [&](auto&& launch) {
+    if constexpr (CAP) launch(make_attn_cap(a.cap, a.scale));
+    else launch();
+  };
   with_head_dim(a.D, [&](auto dtag) {
     constexpr int D = decltype(dtag)::value;
-    attn_bwd_dq_kernel<D, MOD><<<gq, block, 0, stream>>>(
-        a.q, a.k, a.v, a.dout, a.lse, drow, a.dq, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv,
-        a.scale, a.modarg, a.q_rs, a.k_rs, a.v_rs, a.do_rs, a.dq_rs,
-        a.gran, a.bits, a.range, a.bias, a.doc_start);
+    with_cap([&](auto... cap) {
+      attn_bwd_dq_kernel<D, MOD, CAP><<<gq, block, 0, stream>>>(
+          a.q, a.k, a.v, a.dout, a.lse, drow, a.dq, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv,
+          a.scale, a.modarg, a.q_rs, a.k_rs, a.v_rs, a.do_rs, a.dq_rs,
+          a.gran, a.bits, a.range, a.bias, a.doc_start, cap...);
+    });
     // merged dK+dV at D=128 (D=64 and blockmask keep the split pair)
     if constexpr (D == 128 && MOD != MOD_BLOCKMASK) {
       if (!split) {
-        attn_bwd_dkdv_kernel<D, MOD><<<gkv, block, 0, stream>>>(
-            a.q, a.k, a.v, a.dout, a.lse, drow, a.dk, a.dv, a.slopes, a.B, a.Sq, a.Skv, a.Hq,
-            a.Hkv, a.scale, a.modarg, a.q_rs, a.k_rs, a.v_rs, a.do_rs, a.dk_rs, a.dv_rs,
-            a.doc_end);
+        with_cap([&](auto... cap) {
+          attn_bwd_dkdv_kernel<D, MOD, CAP><<<gkv, block, 0, stream>>>(
+              a.q, a.k, a.v, a.dout, a.lse, drow, a.dk, a.dv, a.slopes, a.B, a.Sq, a.Skv, a.Hq,
+              a.Hkv, a.scale, a.modarg, a.q_rs, a.k_rs, a.v_rs, a.do_rs, a.dk_rs, a.dv_rs,
+              a.doc_end, cap...);
+        });
         return;
       }
     }
     auto dkv = [&](auto want_dk, __hip_bfloat16* out, long out_rs) {
-      attn_bwd_dkv_kernel<D, MOD, decltype(want_dk)::value><<<gkv, block, 0, stream>>>(
-          a.q, a.k, a.v, a.dout, a.lse, drow, out, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv,
-          a.scale, a.modarg, a.q_rs, a.k_rs, a.v_rs, a.do_rs, out_rs,
-          a.gran, a.bits, a.qrange, a.bias, a.doc_end);
+      with_cap([&](auto... cap) {
+        attn_bwd_dkv_kernel<D, MOD, decltype(want_dk)::value, CAP><<<gkv, block, 0, stream>>>(
+            a.q, a.k, a.v, a.dout, a.lse, drow, out, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv,
+            a.scale, a.modarg, a.q_rs, a.k_rs, a.v_rs, a.do_rs, out_rs,
+            a.gran, a.bits, a.qrange, a.bias, a.doc_end, cap...);
+      });
     };
     dkv(std::true_type{}, a.dk, a.dk_rs);
     dkv(std::false_type{}, a.dv, a.dv_rs);
@@ -1227,6 +1322,39 @@ std::vector<at::Tensor> attn_bwd_split(at::Tensor q, at::Tensor k, at::Tensor v,
                                        long modarg, at::Tensor slopes) {
   return attn_bwd_impl("attn_bwd_split", q, k, v, o, dout, lse, scale, mod, modarg, slopes,
                        {}, {}, {}, true);
+}
+
+// Backward of attn_cap_fwd: o and lse are those of the capped scores.
+// attn_cap_bwd takes dq/dk/dv like attn_bwd; attn_cap_bwd_split always runs the
+// split dK / dV kernels.
+std::vector<at::Tensor> attn_cap_bwd_impl(const char* who, at::Tensor q, at::Tensor k,
+                                          at::Tensor v, at::Tensor o, at::Tensor dout,
+                                          at::Tensor lse, double scale, long mod, long modarg,
+                                          double cap, at::Tensor dq, at::Tensor dk, at::Tensor dv,
+                                          bool force_split) {
+  AttnArgs a = bwd_args(who, q, k, v, o, dout, lse, scale, dq, dk, dv);
+  check_cap(who, a, cap);
+  a.modarg = (int)modarg;
+  with_cap_mod(who, mod, [&](auto mtag) {
+    run_bwd<decltype(mtag)::value, true>(a, q, force_split);
+  });
+  return {dq, dk, dv};
+}
+
+std::vector<at::Tensor> attn_cap_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                     at::Tensor dout, at::Tensor lse, double scale, long mod,
+                                     long modarg, double cap,
+                                     OptTensor dq, OptTensor dk, OptTensor dv) {
+  return attn_cap_bwd_impl("attn_cap_bwd", q, k, v, o, dout, lse, scale, mod, modarg, cap,
+                           dq.value_or(at::Tensor()), dk.value_or(at::Tensor()),
+                           dv.value_or(at::Tensor()), false);
+}
+
+std::vector<at::Tensor> attn_cap_bwd_split(at::Tensor q, at::Tensor k, at::Tensor v,
+                                           at::Tensor o, at::Tensor dout, at::Tensor lse,
+                                           double scale, long mod, long modarg, double cap) {
+  return attn_cap_bwd_impl("attn_cap_bwd_split", q, k, v, o, dout, lse, scale, mod, modarg, cap,
+                           {}, {}, {}, true);
 }
 
 // Backward of attn_fwd_blockmask (trainable flex attention): same device mask

@@ -47,7 +47,16 @@ constexpr int QPW = 32;  // q rows per wave
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
-template <int D, int MOD, int KVB>
+// CAP: attention-logit soft-capping, P = softmax(c * tanh(scale * q.k / c)),
+// for MOD_NONE / MOD_CAUSAL / MOD_SLIDING_WINDOW. The cap travels as one
+// trailing AttnCap argument (softcap.h) that the other instantiations do not
+// have at all: their argument block and their code are what they were. st
+// stays RAW (masked elements -inf) on both score paths: tanh is monotonic, so
+// the tile maximum is taken on the raw scores and capped once, and the exp
+// block caps every element in registers right before its exp2. The online
+// maximum and defer-max are kept: the fixed shift c would make a row whose
+// scores all sit at -c sum e^(-2c), which is 0 in fp32 from c ~ 44.
+template <int D, int MOD, int KVB, bool CAP = false, typename... Cap>
 __global__ __launch_bounds__(8 * WAVE) void attn_fwd_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, __hip_bfloat16* __restrict__ o,
@@ -66,7 +75,11 @@ __global__ __launch_bounds__(8 * WAVE) void attn_fwd_kernel(
     const __hip_bfloat16* __restrict__ bias = nullptr,
     // MOD_DOCUMENT only: doc_start int32 [B,Sq], first position of each
     // row's document (non-decreasing along s; same for every head)
-    const int* __restrict__ doc_start = nullptr) {
+    const int* __restrict__ doc_start = nullptr, Cap... cap) {
+  static_assert(sizeof...(Cap) == (CAP ? 1 : 0), "CAP takes (AttnCap cap)");
+  static_assert(!CAP || MOD == MOD_NONE || MOD == MOD_CAUSAL || MOD == MOD_SLIDING_WINDOW,
+                "capped instantiations: none, causal, sliding window");
+  [[maybe_unused]] const AttnCap cp = attn_cap_arg(cap...);
   constexpr int NW = 8;  // waves per block
   constexpr int TPB = NW * WAVE;
   constexpr int QPB = NW * QPW;
@@ -315,7 +328,20 @@ __global__ __launch_bounds__(8 * WAVE) void attn_fwd_kernel(
                       KT > 1 ? fmaxf(st[1][i], st[1][i + 8]) : -INFINITY);
 #pragma unroll
       for (int i = 0; i < 4; ++i) tm[i] = fmaxf(tm[i], tm[i + 4]);
-      tmax = fmaxf(fmaxf(tm[0], tm[1]), fmaxf(tm[2], tm[3])) * scale2;
+      tmax = fmaxf(fmaxf(tm[0], tm[1]), fmaxf(tm[2], tm[3]));
+      if constexpr (!CAP) tmax *= scale2;
+    } else if constexpr (CAP) {
+      // masked path, capped: st stays raw, masked elements become -inf
+      tmax = -INFINITY;
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const int k_pos = kv0 + kt * 32 + acc_row(reg, hi);
+          const bool keep = q_valid && attn_keep<MOD>(q_pos, k_pos, Skv, modarg);
+          st[kt][reg] = keep ? st[kt][reg] : -INFINITY;
+          tmax = fmaxf(tmax, st[kt][reg]);
+        }
     } else {
       // masked path: materialize base-2 scores in place of st
       tmax = -INFINITY;
@@ -345,6 +371,9 @@ __global__ __launch_bounds__(8 * WAVE) void attn_fwd_kernel(
         }
     }
     tmax = cross32_max(tmax);
+    // CAP: the raw maximum, capped once (a row with no kept key stays -inf)
+    if constexpr (CAP)
+      tmax = (tmax == -INFINITY) ? -INFINITY : softcap_val(tmax, cp.c2, cp.sic);
     // defer-max (guide T13): while no lane's tile max exceeds the running
     // max by more than THR (base-2), keep the old max and SKIP the O/l
     // rescale entirely — P is then bounded by 2^THR, which the fp32
@@ -357,7 +386,7 @@ __global__ __launch_bounds__(8 * WAVE) void attn_fwd_kernel(
     // branchless forms so [PV MFMAs + exp + psum + pack] is ONE basic block
     // (a branch splits the scheduling region and exiles the VALU from the
     // MFMA issue gaps): masked-path st is pre-scaled, so sc2 folds to 1.
-    const float sc2 = full ? scale2 : 1.0f;
+    [[maybe_unused]] const float sc2 = full ? scale2 : 1.0f;
     // alpha == 1 exactly when defer (mc == m_old); exp2(-inf)=0 at tile 0.
     const float alpha = __builtin_amdgcn_exp2f(m_old - mc);
 
@@ -391,7 +420,13 @@ __global__ __launch_bounds__(8 * WAVE) void attn_fwd_kernel(
     for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        p[kt][reg] = __builtin_amdgcn_exp2f(fmaf(st[kt][reg], sc2, -mc));
+        if constexpr (CAP) {
+          // a select, not a branch: -inf marks a masked element on both paths
+          const float e = __builtin_amdgcn_exp2f(softcap_val(st[kt][reg], cp.c2, cp.sic) - mc);
+          p[kt][reg] = (st[kt][reg] == -INFINITY) ? 0.f : e;
+        } else {
+          p[kt][reg] = __builtin_amdgcn_exp2f(fmaf(st[kt][reg], sc2, -mc));
+        }
         psum += p[kt][reg];
       }
     psum = cross32_sum(psum);
@@ -463,7 +498,7 @@ __global__ __launch_bounds__(8 * WAVE) void attn_fwd_kernel(
 }
 
 // The one forward launch: 8 waves per block of 256 q rows.
-template <int MOD>
+template <int MOD, bool CAP = false>
 void run_fwd(const AttnArgs& a) {
   constexpr int QPB = 8 * QPW;
   const dim3 grid(cdiv(a.Sq, QPB), a.Hq, a.B), block(8 * WAVE);
@@ -473,10 +508,20 @@ void run_fwd(const AttnArgs& a) {
     // D=64 runs 128-row tiles: twice the MFMAs per barrier at the same
     // occupancy (234 VGPR, no spill) — fwd 312 -> 363 TF at the 124M shape.
     // D=128 has no VGPRs for them; the blockmask granules are 64 columns.
-    constexpr int KVB = (D == 64 && MOD != MOD_BLOCKMASK) ? 128 : 64;
-    attn_fwd_kernel<D, MOD, KVB><<<grid, block, 0, stream>>>(
-        a.q, a.k, a.v, a.o, a.lse, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv, a.scale, a.modarg,
-        a.q_rs, a.k_rs, a.v_rs, a.gran, a.bits, a.range, a.bias, a.doc_start);
+    // The capped sliding window at D=64 also stays at 64: with 128-row tiles
+    // it needs 256 VGPRs plus 140 B of scratch.
+    constexpr int KVB = (D == 64 && MOD != MOD_BLOCKMASK &&
+                         !(CAP && MOD == MOD_SLIDING_WINDOW)) ? 128 : 64;
+    if constexpr (CAP) {
+      attn_fwd_kernel<D, MOD, KVB, true><<<grid, block, 0, stream>>>(
+          a.q, a.k, a.v, a.o, a.lse, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv, a.scale, a.modarg,
+          a.q_rs, a.k_rs, a.v_rs, a.gran, a.bits, a.range, a.bias, a.doc_start,
+          make_attn_cap(a.cap, a.scale));
+    } else {
+      attn_fwd_kernel<D, MOD, KVB><<<grid, block, 0, stream>>>(
+          a.q, a.k, a.v, a.o, a.lse, a.slopes, a.B, a.Sq, a.Skv, a.Hq, a.Hkv, a.scale, a.modarg,
+          a.q_rs, a.k_rs, a.v_rs, a.gran, a.bits, a.range, a.bias, a.doc_start);
+    }
   });
 }
 
@@ -510,6 +555,18 @@ std::vector<at::Tensor> attn_fwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, d
   AttnArgs a = fwd_args("attn_fwd_doc", q, k, v, scale, o, lse);
   a.doc_start = check_doc("attn_fwd_doc", a, q, doc_start, "doc_start");
   run_fwd<MOD_DOCUMENT>(a);
+  return {o, lse};
+}
+
+// attn_fwd with the scores soft-capped: P = softmax(cap * tanh(scale * q.k / cap)),
+// lse of the capped scores. mod: none, causal or sliding window.
+std::vector<at::Tensor> attn_cap_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
+                                     long mod, long modarg, double cap) {
+  at::Tensor o, lse;
+  AttnArgs a = fwd_args("attn_cap_fwd", q, k, v, scale, o, lse);
+  check_cap("attn_cap_fwd", a, cap);
+  a.modarg = (int)modarg;
+  with_cap_mod("attn_cap_fwd", mod, [&](auto mtag) { run_fwd<decltype(mtag)::value, true>(a); });
   return {o, lse};
 }
 

@@ -5,8 +5,10 @@
 // entry point's name for the error text.
 #pragma once
 #include <torch/extension.h>
+#include <cmath>
 #include <type_traits>
 #include "attn_common.h"
+#include "softcap.h"
 
 // Everything the attention kernels take, in one plain struct. It is filled by
 // the checks below and unpacked at the one launch site of each kernel; the
@@ -18,6 +20,7 @@ struct AttnArgs {
   int B, Sq, Skv, Hq, Hkv, D;
   float scale;
   int modarg = 0;
+  double cap = 0.;  // attention-logit soft-cap of the attn_cap_* entry points
   long q_rs, k_rs, v_rs;  // row strides of the [B,S,H,D] views (elements)
   // MOD_BLOCKMASK only (layouts: attn_fwd.hip); qrange is backward-only
   const unsigned char *gran = nullptr, *bits = nullptr;
@@ -71,6 +74,28 @@ void with_mod(const char* who, long mod, F&& f) {
     case MOD_ALIBI: f(std::integral_constant<int, MOD_ALIBI>{}); break;
     default: TORCH_CHECK(false, who, ": unknown mod ", mod);
   }
+}
+
+// the three mod codes that have capped instantiations
+template <class F>
+void with_cap_mod(const char* who, long mod, F&& f) {
+  switch (mod) {
+    case MOD_NONE: f(std::integral_constant<int, MOD_NONE>{}); break;
+    case MOD_CAUSAL: f(std::integral_constant<int, MOD_CAUSAL>{}); break;
+    case MOD_SLIDING_WINDOW: f(std::integral_constant<int, MOD_SLIDING_WINDOW>{}); break;
+    default:
+      TORCH_CHECK(false, who, ": soft-capping is built for mod none, causal and sliding "
+                  "window, got mod ", mod);
+  }
+}
+
+// the soft-cap of the attn_cap_* entry points: finite and > 0, with a scale
+// > 0 (the kernels take the sign of a capped score from the raw q.k)
+inline void check_cap(const char* who, AttnArgs& a, double cap) {
+  TORCH_CHECK(std::isfinite(cap) && cap > 0., who, ": cap must be finite and > 0, got ", cap);
+  TORCH_CHECK(std::isfinite(a.scale) && a.scale > 0.f, who, ": soft-capping needs scale > 0, got ",
+              a.scale);
+  a.cap = cap;
 }
 
 inline bool shape_is(const at::Tensor& t, long a, long b, long c, long d) {

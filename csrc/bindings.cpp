@@ -92,6 +92,17 @@ std::vector<at::Tensor> attn_bwd_doc(at::Tensor q, at::Tensor k, at::Tensor v, a
                                      at::Tensor dout, at::Tensor lse, double scale,
                                      at::Tensor doc_start, at::Tensor doc_end,
                                      OptTensor dq, OptTensor dk, OptTensor dv);
+// attention-logit soft-capping: scores cap * tanh(scale * q.k / cap); mod none,
+// causal or sliding window
+std::vector<at::Tensor> attn_cap_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
+                                     long mod, long modarg, double cap);
+std::vector<at::Tensor> attn_cap_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                     at::Tensor dout, at::Tensor lse, double scale, long mod,
+                                     long modarg, double cap,
+                                     OptTensor dq, OptTensor dk, OptTensor dv);
+std::vector<at::Tensor> attn_cap_bwd_split(at::Tensor q, at::Tensor k, at::Tensor v,
+                                           at::Tensor o, at::Tensor dout, at::Tensor lse,
+                                           double scale, long mod, long modarg, double cap);
 // sampling.hip
 at::Tensor sample_token(at::Tensor logits, double temperature, double top_p, double min_p,
                         long seed);
@@ -109,6 +120,11 @@ void kv_append_q8_(at::Tensor k, at::Tensor v, at::Tensor kc, at::Tensor ksz,
                    at::Tensor vc, at::Tensor vsz, at::Tensor pos);
 at::Tensor attn_decode_q8(at::Tensor q, at::Tensor kc, at::Tensor ksz, at::Tensor vc,
                           at::Tensor vsz, at::Tensor pos, at::Tensor part, double scale);
+at::Tensor attn_decode_cap(at::Tensor q, at::Tensor kc, at::Tensor vc, at::Tensor pos,
+                           at::Tensor part, double scale, double cap);
+at::Tensor attn_decode_q8_cap(at::Tensor q, at::Tensor kc, at::Tensor ksz, at::Tensor vc,
+                              at::Tensor vsz, at::Tensor pos, at::Tensor part, double scale,
+                              double cap);
 // gemv.hip
 at::Tensor gemv_bf16(at::Tensor x, at::Tensor W);
 at::Tensor gemv_ex(at::Tensor x, at::Tensor W, long mode, at::Tensor nw, double eps,
@@ -180,6 +196,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "backward of attn_fwd_doc (dq, dk, dv); dq/dk/dv as in attn_bwd",
         "q"_a, "k"_a, "v"_a, "o"_a, "dout"_a, "lse"_a, "scale"_a, "doc_start"_a, "doc_end"_a,
         "dq"_a = py::none(), "dk"_a = py::none(), "dv"_a = py::none());
+  m.def("attn_cap_fwd", &attn_cap_fwd,
+        "attn_fwd of the soft-capped scores cap * tanh(scale * q.k / cap) (o, lse)");
+  m.def("attn_cap_bwd", &attn_cap_bwd,
+        "backward of attn_cap_fwd (dq, dk, dv); dq/dk/dv as in attn_bwd",
+        "q"_a, "k"_a, "v"_a, "o"_a, "dout"_a, "lse"_a, "scale"_a, "mod"_a, "modarg"_a, "cap"_a,
+        "dq"_a = py::none(), "dk"_a = py::none(), "dv"_a = py::none());
+  m.def("attn_cap_bwd_split", &attn_cap_bwd_split,
+        "attn_cap_bwd on the split dK / dV kernels");
+  m.def("attn_decode_cap", &attn_decode_cap, "attn_decode of the soft-capped scores");
+  m.def("attn_decode_q8_cap", &attn_decode_q8_cap, "attn_decode_q8 of the soft-capped scores");
   m.def("sample_token", &sample_token, "fused temperature/min-p sampling");
   m.def("sample_token_dev", &sample_token_dev,
         "graph-capturable sampling (device position salt)");

@@ -16,7 +16,7 @@
 // q/k/v of the new token [B, 1, H, D].
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "attn_launch.h"
 
 namespace {
 
@@ -84,14 +84,20 @@ __global__ void kv_append_kernel(const __hip_bfloat16* __restrict__ k,
 // current length exit early (l=0). D <= 128. Memory-level parallelism is
 // the whole game here (PMC: WAIT_ANY 84%, VALU 0.3% on the naive version):
 // both passes keep UNR independent loads in flight per lane.
-template <int D, int CHUNK>
+// CAP: attention-logit soft-capping. The score written to s_row is the capped
+// one, c * tanh(scale * q.k / c) in base 2 (softcap.h); everything after it,
+// the combine kernel included, is unchanged. The cap is one trailing AttnCap
+// argument that the uncapped instantiations do not have.
+template <int D, int CHUNK, bool CAP = false, typename... Cap>
 __global__ __launch_bounds__(256) void attn_decode_partial_kernel(
     const __hip_bfloat16* __restrict__ q,   // [B, Hq, D] (new token, roped)
     const __hip_bfloat16* __restrict__ kc,  // [B, Lmax, Hkv, D]
     const __hip_bfloat16* __restrict__ vc,
     const int* __restrict__ pos,            // length BEFORE append
     float* __restrict__ part,               // [B, Hq, NC, D+2]
-    int B, int Lmax, int Hq, int Hkv, float scale2) {
+    int B, int Lmax, int Hq, int Hkv, float scale2, Cap... cap) {
+  static_assert(sizeof...(Cap) == (CAP ? 1 : 0), "CAP takes (AttnCap cap)");
+  [[maybe_unused]] const AttnCap cp = attn_cap_arg(cap...);
   const int chunk = blockIdx.x, hq = blockIdx.y, b = blockIdx.z;
   const int NC = gridDim.x;
   const int hkv = hq / (Hq / Hkv);
@@ -142,7 +148,10 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(
       for (int j = 0; j < 8; ++j)
         acc += bf16_bits_to_f32(qv.s[j]) * bf16_bits_to_f32(kv8[u].s[j]);
       for (int off = lpr / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-      if (krow[u] < kend && (lane % lpr) == 0) s_row[krow[u] - k0] = acc * scale2;
+      if (krow[u] < kend && (lane % lpr) == 0) {
+        if constexpr (CAP) s_row[krow[u] - k0] = softcap_val(acc, cp.c2, cp.sic);
+        else s_row[krow[u] - k0] = acc * scale2;
+      }
     }
   }
   __syncthreads();
@@ -271,13 +280,16 @@ __global__ void kv_append_q8_kernel(const __hip_bfloat16* __restrict__ k,
   if (lane == 0) (t == 0 ? ksz : vsz)[row * (D / G) + grp] = float2{scale, lo};
 }
 
-template <int D, int CHUNK>
+// CAP: as in attn_decode_partial_kernel.
+template <int D, int CHUNK, bool CAP = false, typename... Cap>
 __global__ __launch_bounds__(256) void attn_decode_partial_q8_kernel(
     const __hip_bfloat16* __restrict__ q,
     const unsigned char* __restrict__ kc, const float2* __restrict__ ksz,
     const unsigned char* __restrict__ vc, const float2* __restrict__ vsz,
     const int* __restrict__ pos, float* __restrict__ part,
-    int B, int Lmax, int Hq, int Hkv, float scale2) {
+    int B, int Lmax, int Hq, int Hkv, float scale2, Cap... cap) {
+  static_assert(sizeof...(Cap) == (CAP ? 1 : 0), "CAP takes (AttnCap cap)");
+  [[maybe_unused]] const AttnCap cp = attn_cap_arg(cap...);
   // same MLP-pipelined structure as the bf16 kernel (UNR loads in flight),
   // with the int8 group dequant fused into both passes
   const int chunk = blockIdx.x, hq = blockIdx.y, b = blockIdx.z;
@@ -334,7 +346,10 @@ __global__ __launch_bounds__(256) void attn_decode_partial_q8_kernel(
       for (int j = 0; j < 8; ++j)
         acc += bf16_bits_to_f32(qv.s[j]) * (cb[j] * sz[u].x + sz[u].y);
       for (int off = lpr / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-      if (krow[u] < kend && (lane % lpr) == 0) s_row[krow[u] - k0] = acc * scale2;
+      if (krow[u] < kend && (lane % lpr) == 0) {
+        if constexpr (CAP) s_row[krow[u] - k0] = softcap_val(acc, cp.c2, cp.sic);
+        else s_row[krow[u] - k0] = acc * scale2;
+      }
     }
   }
   __syncthreads();
@@ -433,8 +448,25 @@ void kv_append_(at::Tensor k, at::Tensor v, at::Tensor kc, at::Tensor vc, at::Te
       pos.data_ptr<int>(), B, Lmax, Hkv, D);
 }
 
-at::Tensor attn_decode(at::Tensor q, at::Tensor kc, at::Tensor vc, at::Tensor pos,
-                       at::Tensor part, double scale) {
+namespace {
+
+// launch(cap...) with the folded cap argument when CAP (cap checked finite and
+// > 0, scale > 0: attn_launch.h check_cap), with nothing otherwise
+template <bool CAP, class F>
+void decode_with_cap(const char* who, double scale, double cap, F&& launch) {
+  if constexpr (CAP) {
+    AttnArgs a;
+    a.scale = (float)scale;
+    check_cap(who, a, cap);
+    launch(make_attn_cap(a.cap, scale));
+  } else {
+    launch();
+  }
+}
+
+template <bool CAP>
+at::Tensor attn_decode_impl(const char* who, at::Tensor q, at::Tensor kc, at::Tensor vc,
+                            at::Tensor pos, at::Tensor part, double scale, double cap) {
   // q: [B, 1, Hq, D]; kc/vc: [B, Lmax, Hkv, D]; part: fp32 workspace
   // [B, Hq, NC, D+2] with NC = cdiv(Lmax, CHUNK). Returns o [B, 1, Hq, D].
   constexpr int CHUNK = 256;
@@ -442,8 +474,9 @@ at::Tensor attn_decode(at::Tensor q, at::Tensor kc, at::Tensor vc, at::Tensor po
   const int B = kc.size(0), Lmax = kc.size(1), Hkv = kc.size(2), D = kc.size(3);
   const int Hq = q.size(2);
   const int NC = cdiv(Lmax, CHUNK);
-  TORCH_CHECK(NC <= 64, "attn_decode: Lmax too large for the combine kernel");
-  TORCH_CHECK(part.numel() >= (long)B * Hq * NC * (D + 2), "attn_decode: workspace too small");
+  TORCH_CHECK(NC <= 64, who, ": Lmax too large for the combine kernel");
+  TORCH_CHECK(part.numel() >= (long)B * Hq * NC * (D + 2), who, ": workspace too small");
+  TORCH_CHECK(D == 64 || D == 128, who, ": head_dim must be 64 or 128");
   auto o = at::empty({B, 1, Hq, D}, q.options());
   auto stream = at::cuda::getCurrentHIPStream();
   const float scale2 = (float)scale * LOG2E;
@@ -452,20 +485,30 @@ at::Tensor attn_decode(at::Tensor q, at::Tensor kc, at::Tensor vc, at::Tensor po
   auto* kp = reinterpret_cast<const __hip_bfloat16*>(kc.data_ptr());
   auto* vp = reinterpret_cast<const __hip_bfloat16*>(vc.data_ptr());
   auto* op = reinterpret_cast<__hip_bfloat16*>(o.data_ptr());
-  if (D == 128) {
-    attn_decode_partial_kernel<128, CHUNK><<<gA, 256, 0, stream>>>(
-        qp, kp, vp, pos.data_ptr<int>(), part.data_ptr<float>(), B, Lmax, Hq, Hkv, scale2);
-    attn_decode_combine_kernel<128><<<dim3(Hq, B), 128, 0, stream>>>(
-        part.data_ptr<float>(), op, pos.data_ptr<int>(), NC, Hq, CHUNK);
-  } else if (D == 64) {
-    attn_decode_partial_kernel<64, CHUNK><<<gA, 256, 0, stream>>>(
-        qp, kp, vp, pos.data_ptr<int>(), part.data_ptr<float>(), B, Lmax, Hq, Hkv, scale2);
-    attn_decode_combine_kernel<64><<<dim3(Hq, B), 128, 0, stream>>>(
-        part.data_ptr<float>(), op, pos.data_ptr<int>(), NC, Hq, CHUNK);
-  } else {
-    TORCH_CHECK(false, "attn_decode: head_dim must be 64 or 128");
-  }
+  decode_with_cap<CAP>(who, scale, cap, [&](auto... cp) {
+    with_head_dim(D, [&](auto dtag) {
+      constexpr int HD = decltype(dtag)::value;
+      attn_decode_partial_kernel<HD, CHUNK, CAP><<<gA, 256, 0, stream>>>(
+          qp, kp, vp, pos.data_ptr<int>(), part.data_ptr<float>(), B, Lmax, Hq, Hkv, scale2,
+          cp...);
+      attn_decode_combine_kernel<HD><<<dim3(Hq, B), 128, 0, stream>>>(
+          part.data_ptr<float>(), op, pos.data_ptr<int>(), NC, Hq, CHUNK);
+    });
+  });
   return o;
+}
+
+}  // namespace
+
+at::Tensor attn_decode(at::Tensor q, at::Tensor kc, at::Tensor vc, at::Tensor pos,
+                       at::Tensor part, double scale) {
+  return attn_decode_impl<false>("attn_decode", q, kc, vc, pos, part, scale, 0.);
+}
+
+// attn_decode with the scores soft-capped: cap * tanh(scale * q.k / cap)
+at::Tensor attn_decode_cap(at::Tensor q, at::Tensor kc, at::Tensor vc, at::Tensor pos,
+                           at::Tensor part, double scale, double cap) {
+  return attn_decode_impl<true>("attn_decode_cap", q, kc, vc, pos, part, scale, cap);
 }
 
 
@@ -483,36 +526,54 @@ void kv_append_q8_(at::Tensor k, at::Tensor v, at::Tensor kc, at::Tensor ksz,
       pos.data_ptr<int>(), B, Lmax, Hkv, D);
 }
 
-at::Tensor attn_decode_q8(at::Tensor q, at::Tensor kc, at::Tensor ksz, at::Tensor vc,
-                          at::Tensor vsz, at::Tensor pos, at::Tensor part, double scale) {
+namespace {
+
+template <bool CAP>
+at::Tensor attn_decode_q8_impl(const char* who, at::Tensor q, at::Tensor kc, at::Tensor ksz,
+                               at::Tensor vc, at::Tensor vsz, at::Tensor pos, at::Tensor part,
+                               double scale, double cap) {
   constexpr int CHUNK = 256;
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16);
   const int B = kc.size(0), Lmax = kc.size(1), Hkv = kc.size(2), D = kc.size(3);
   const int Hq = q.size(2);
   const int NC = cdiv(Lmax, CHUNK);
-  TORCH_CHECK(NC <= 64, "attn_decode_q8: Lmax too large");
+  TORCH_CHECK(NC <= 64, who, ": Lmax too large");
+  TORCH_CHECK(D == 64 || D == 128, who, ": head_dim must be 64 or 128");
   auto o = at::empty({B, 1, Hq, D}, q.options());
   auto stream = at::cuda::getCurrentHIPStream();
   const float scale2 = (float)scale * LOG2E;
   dim3 gA(NC, Hq, B);
   auto* qp = reinterpret_cast<const __hip_bfloat16*>(q.contiguous().data_ptr());
   auto* op = reinterpret_cast<__hip_bfloat16*>(o.data_ptr());
-#define Q8LAUNCH(D_)                                                                     \
-  do {                                                                                   \
-    attn_decode_partial_q8_kernel<D_, CHUNK><<<gA, 256, 0, stream>>>(                    \
-        qp, kc.data_ptr<unsigned char>(),                                                \
-        reinterpret_cast<const float2*>(ksz.data_ptr<float>()),                          \
-        vc.data_ptr<unsigned char>(),                                                    \
-        reinterpret_cast<const float2*>(vsz.data_ptr<float>()), pos.data_ptr<int>(),     \
-        part.data_ptr<float>(), B, Lmax, Hq, Hkv, scale2);                               \
-    attn_decode_combine_kernel<D_><<<dim3(Hq, B), 128, 0, stream>>>(                     \
-        part.data_ptr<float>(), op, pos.data_ptr<int>(), NC, Hq, CHUNK);                 \
-  } while (0)
-  if (D == 128) Q8LAUNCH(128);
-  else if (D == 64) Q8LAUNCH(64);
-  else TORCH_CHECK(false, "attn_decode_q8: head_dim must be 64 or 128");
-#undef Q8LAUNCH
+  decode_with_cap<CAP>(who, scale, cap, [&](auto... cp) {
+    with_head_dim(D, [&](auto dtag) {
+      constexpr int HD = decltype(dtag)::value;
+      attn_decode_partial_q8_kernel<HD, CHUNK, CAP><<<gA, 256, 0, stream>>>(
+          qp, kc.data_ptr<unsigned char>(),
+          reinterpret_cast<const float2*>(ksz.data_ptr<float>()),
+          vc.data_ptr<unsigned char>(),
+          reinterpret_cast<const float2*>(vsz.data_ptr<float>()), pos.data_ptr<int>(),
+          part.data_ptr<float>(), B, Lmax, Hq, Hkv, scale2, cp...);
+      attn_decode_combine_kernel<HD><<<dim3(Hq, B), 128, 0, stream>>>(
+          part.data_ptr<float>(), op, pos.data_ptr<int>(), NC, Hq, CHUNK);
+    });
+  });
   return o;
+}
+
+}  // namespace
+
+at::Tensor attn_decode_q8(at::Tensor q, at::Tensor kc, at::Tensor ksz, at::Tensor vc,
+                          at::Tensor vsz, at::Tensor pos, at::Tensor part, double scale) {
+  return attn_decode_q8_impl<false>("attn_decode_q8", q, kc, ksz, vc, vsz, pos, part, scale, 0.);
+}
+
+// attn_decode_q8 with the scores soft-capped, as attn_decode_cap
+at::Tensor attn_decode_q8_cap(at::Tensor q, at::Tensor kc, at::Tensor ksz, at::Tensor vc,
+                              at::Tensor vsz, at::Tensor pos, at::Tensor part, double scale,
+                              double cap) {
+  return attn_decode_q8_impl<true>("attn_decode_q8_cap", q, kc, ksz, vc, vsz, pos, part, scale,
+                                   cap);
 }
 
 void pos_incr_(at::Tensor pos) {

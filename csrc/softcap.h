@@ -35,3 +35,24 @@ __device__ __forceinline__ float softcap_dfac(float t, float inv_c) {
   const float r = t * inv_c;
   return fmaf(-r, r, 1.f);
 }
+
+// Attention-logit soft-capping (attn_fwd.hip, attn_bwd.hip, decode.hip): the
+// kernels hold scores as raw q.k accumulators and exponentiate in base 2, so
+// the cap travels pre-folded, computed once on the host:
+//   t * log2(e) = softcap_val(acc, c2, sic)   with x = scale * acc
+//   d t / d x   = softcap_dfac(t * log2(e), inv_c2)
+// scale > 0, so acc carries the sign of x. One by-value kernel argument of
+// the capped instantiations only (the trailing pack, as in cross_entropy.hip);
+// it is wave-uniform and stays in SGPRs.
+struct AttnCap {
+  float c2;      // c * log2(e)
+  float sic;     // scale / c
+  float inv_c2;  // 1 / (c * log2(e))
+};
+inline AttnCap make_attn_cap(double cap, double scale) {
+  constexpr double LOG2E_D = 1.4426950408889634;
+  return {(float)(cap * LOG2E_D), (float)(scale / cap), (float)(1.0 / (cap * LOG2E_D))};
+}
+// the trailing cap argument of a CAP kernel; the others pass nothing
+__device__ __forceinline__ AttnCap attn_cap_arg() { return {0.f, 0.f, 0.f}; }
+__device__ __forceinline__ AttnCap attn_cap_arg(AttnCap c) { return c; }

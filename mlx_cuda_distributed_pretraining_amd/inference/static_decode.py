@@ -56,6 +56,10 @@ class StaticLayerCache:
         trad = attn.args.rope_traditional
         qk_norm = getattr(attn.args, "qk_norm", False)
         eps = attn.args.rms_norm_eps
+        # attention-logit soft-capping: the _cap decode kernels / the capped
+        # reference (same launches and workspace, so nothing new is allocated
+        # under graph capture)
+        softcap = getattr(attn.args, "attn_logit_softcap", None)
 
         if use_hip(qkv, dtypes=(torch.bfloat16,)):
             ext = get_ext()
@@ -84,9 +88,14 @@ class StaticLayerCache:
                 ksz = ow.ksz[self.idx].view(B, -1)
                 vsz = ow.vsz[self.idx].view(B, -1)
                 ext.kv_append_q8_(k, v, kc, ksz, vc, vsz, ow.pos)
+                if softcap is not None:
+                    return ext.attn_decode_q8_cap(q, kc, ksz, vc, vsz, ow.pos, ow.part,
+                                                  attn.scale, softcap)
                 return ext.attn_decode_q8(q, kc, ksz, vc, vsz, ow.pos, ow.part,
                                           attn.scale)
             ext.kv_append_(k, v, kc, vc, ow.pos)
+            if softcap is not None:
+                return ext.attn_decode_cap(q, kc, vc, ow.pos, ow.part, attn.scale, softcap)
             return ext.attn_decode(q, kc, vc, ow.pos, ow.part, attn.scale)
 
         q = qkv[..., : Hq * D].view(B, 1, Hq, D).contiguous()
@@ -125,11 +134,11 @@ class StaticLayerCache:
             quant_row(v, vc, ow.vsz[self.idx])
             kd = dequant(kc, ow.ksz[self.idx], p + 1)
             vd = dequant(vc, ow.vsz[self.idx], p + 1)
-            return attention_ref(q, kd, vd, causal=True, scale=attn.scale)
+            return attention_ref(q, kd, vd, causal=True, scale=attn.scale, softcap=softcap)
         kc[:, p : p + 1] = k
         vc[:, p : p + 1] = v
         return attention_ref(q, kc[:, : p + 1], vc[:, : p + 1], causal=True,
-                             scale=attn.scale)
+                             scale=attn.scale, softcap=softcap)
 
 
 class StaticDecodeState:

@@ -59,6 +59,10 @@ class ModelArgs:
     # final-logit soft-capping, logits = c * tanh(logits / c) after logit_scale
     # (Gemma-2; ops/softcap.py). None or 0 = off.
     logit_softcap: Optional[float] = None
+    # attention-logit soft-capping, scores = c * tanh(scores / c) after the
+    # 1/sqrt(D) scale and before masking (Gemma-2: 50; ops/attention.py
+    # flash_attention). None or 0 = off. Masks: causal and sliding window.
+    attn_logit_softcap: Optional[float] = None
     attention_type: str = "flash"  # flash | flex | simple
     attention_window: Optional[int] = None  # sliding-window size (flex)
     attention_prefix_len: Optional[int] = None  # prefix-LM split (flex)
@@ -85,6 +89,16 @@ class ModelArgs:
                 raise ValueError(
                     f"model.misc.logit_softcap must be finite and >= 0 (0 = off), got {c}")
             self.logit_softcap = c or None
+        if self.attn_logit_softcap is not None:
+            c = float(self.attn_logit_softcap)
+            if not (math.isfinite(c) and c >= 0.0):
+                raise ValueError(
+                    f"model.attention.logit_softcap must be finite and >= 0 (0 = off), got {c}")
+            self.attn_logit_softcap = c or None
+        if self.attn_logit_softcap is not None and (
+                self.use_alibi or self.attention_prefix_len is not None):
+            raise ValueError("model.attention.logit_softcap cannot be combined with alibi or "
+                             "prefix_len: there are no capped kernels for those masks")
 
     @classmethod
     def from_config(cls, model_cfg: Any, vocab_size: int) -> "ModelArgs":
@@ -111,6 +125,7 @@ class ModelArgs:
             tie_word_embeddings=bool(misc.get("tie_word_embeddings", True)),
             logit_scale=misc.get("logit_scale"),
             logit_softcap=misc.get("logit_softcap"),
+            attn_logit_softcap=attn.get("logit_softcap"),
             fp8=bool(misc.get("fp8", False)),
             router_aux_loss_coef=float(misc.get("router_aux_loss_coef", 0.01)),
             attention_type=str(attn.get("type", "flash")),
@@ -215,6 +230,10 @@ class Attention(nn.Module):
             if self.flex_mask is not None:
                 raise ValueError("document mask (doc_start) cannot be combined with a "
                                  "flex mask (Model.set_flex_mask)")
+            if self.args.attn_logit_softcap is not None:
+                raise ValueError("document mask (doc_start) cannot be combined with "
+                                 "model.attention.logit_softcap: there are no capped "
+                                 "document-mask kernels")
         if getattr(self, "_sp", False) and self.training:
             x = gather_sp(x)  # SP: S-sharded stream -> full sequence
         elif getattr(self, "_tp", False):
@@ -259,6 +278,7 @@ class Attention(nn.Module):
                 q_norm_weight=self.q_norm.weight if self.args.qk_norm else None,
                 k_norm_weight=self.k_norm.weight if self.args.qk_norm else None,
                 norm_eps=self.args.rms_norm_eps,
+                softcap=self.args.attn_logit_softcap,
             )
             return self._project_out(o)
 
@@ -273,7 +293,8 @@ class Attention(nn.Module):
         atype = self.args.attention_type
         if atype == "simple":
             # reference SimpleAttention parity path (fp32 composition)
-            o = attention_ref(q, k, v, causal=True, scale=self.scale, doc_start=doc_start)
+            o = attention_ref(q, k, v, causal=True, scale=self.scale, doc_start=doc_start,
+                              softcap=self.args.attn_logit_softcap)
         else:
             o = flash_attention(
                 q, k, v,
@@ -282,6 +303,7 @@ class Attention(nn.Module):
                 window=self.args.attention_window if atype == "flex" else None,
                 prefix_len=self.args.attention_prefix_len if atype == "flex" else None,
                 alibi_slopes=self.alibi_slopes if self.args.use_alibi else None,
+                softcap=self.args.attn_logit_softcap,
             )
         return self._project_out(o)
 
@@ -574,8 +596,13 @@ class Model(nn.Module):
         needs at least one live key (see ``flex_attention``). It applies to
         full-sequence forwards only: the KV-cache and static-decode paths
         ignore it. The attention_type "simple" parity path is bypassed while
-        a mask is set.
+        a mask is set. A model with ``attention.logit_softcap`` refuses a mask
+        (``ValueError``): the blockmask kernels have no capped variant.
         """
+        if mask is not None and self.args.attn_logit_softcap is not None:
+            raise ValueError("set_flex_mask cannot be combined with "
+                             "model.attention.logit_softcap: the blockmask kernels have no "
+                             "capped variant")
         for layer in self.layers:
             layer.attention.flex_mask = mask
 

@@ -53,6 +53,7 @@ def attention_ref(
     mask_mod: Optional[Callable] = None,
     return_lse: bool = False,
     doc_start: Optional[torch.Tensor] = None,
+    softcap: Optional[float] = None,
 ):
     """fp32 reference composition (used on CPU and as the test oracle).
 
@@ -65,6 +66,9 @@ def attention_ref(
     score tensor). mask_mod(b, h, q_idx, kv_idx) -> bool keep-mask. Index
     tensors arrive BROADCASTABLE (q [S,1] x kv [1,Skv]); write mods as plain
     expressions over them.
+    softcap: attention-logit soft-capping, ``c * tanh(scores / c)`` on the
+    scaled scores, before ALiBi / ``score_mod`` / masking (see
+    ``flash_attention``).
     """
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
@@ -77,6 +81,8 @@ def attention_ref(
         kf = kf.repeat_interleave(rep, dim=1)
         vf = vf.repeat_interleave(rep, dim=1)
     scores = torch.einsum("bhsd,bhtd->bhst", qf, kf) * scale
+    if softcap is not None:
+        scores = softcap * torch.tanh(scores / softcap)
 
     Skv = k.shape[1]
     # Absolute query positions: with a KV cache, the S query rows sit at the
@@ -178,10 +184,20 @@ class _Mask(NamedTuple):
     slopes: torch.Tensor  # f32 ALiBi slopes [Hq]; empty = no ALiBi
     doc_start: Optional[torch.Tensor]  # int32 contiguous [B, S], or None
     doc_end: Optional[torch.Tensor]  # likewise; set whenever doc_start is
+    softcap: Optional[float] = None  # attention-logit soft-cap c, or None
 
     @classmethod
     def build(cls, causal, window, prefix_len, alibi_slopes, doc_start, doc_end,
-              B: int, Sq: int, Skv: int, Hq: int, device) -> "_Mask":
+              B: int, Sq: int, Skv: int, Hq: int, device, softcap=None) -> "_Mask":
+        if softcap is not None:
+            softcap = float(softcap)
+            if not (math.isfinite(softcap) and softcap > 0):
+                raise ValueError(f"softcap must be finite and > 0 (or None), got {softcap}")
+            # capped kernels exist for none / causal / sliding window only; the
+            # fp32 composition would be a silent O(S^2) fallback in a training run
+            if doc_start is not None or prefix_len is not None or alibi_slopes is not None:
+                raise ValueError("softcap cannot be combined with doc_start, prefix_len or "
+                                 "ALiBi: there are no capped kernels for those masks")
         if alibi_slopes is not None and not isinstance(alibi_slopes, torch.Tensor):
             # an int head count builds the standard 2^(-8(i+1)/H) slopes —
             # matches the reference's loose API
@@ -214,7 +230,7 @@ class _Mask(NamedTuple):
                 doc_end = doc_end.to(device=device, dtype=torch.int32).contiguous()
         slopes = (alibi_slopes.float().contiguous() if alibi_slopes is not None
                   else torch.empty(0, dtype=torch.float32, device=device))
-        return cls(causal, window, prefix_len, slopes, doc_start, doc_end)
+        return cls(causal, window, prefix_len, slopes, doc_start, doc_end, softcap)
 
     @property
     def mod(self) -> int:
@@ -228,27 +244,34 @@ class _Mask(NamedTuple):
     def save(self, ctx, *tensors):
         """ctx.save_for_backward of a node's own tensors followed by the
         mask's; ``load`` undoes it."""
-        ctx.save_for_backward(*tensors, *self[3:])
-        ctx.mask_meta = self[:3]
+        ctx.save_for_backward(*tensors, *self[3:6])
+        ctx.mask_meta = (*self[:3], self.softcap)
 
     @classmethod
     def load(cls, ctx):
         *tensors, slopes, doc_start, doc_end = ctx.saved_tensors
-        return cls(*ctx.mask_meta, slopes, doc_start, doc_end), tensors
+        *meta, softcap = ctx.mask_meta
+        return cls(*meta, slopes, doc_start, doc_end, softcap), tensors
 
     def ref(self, q, k, v, scale, return_lse=False):
         return attention_ref(q, k, v, causal=self.causal, scale=scale, window=self.window,
                              prefix_len=self.prefix_len,
                              alibi_slopes=self.slopes if self.slopes.numel() else None,
-                             return_lse=return_lse, doc_start=self.doc_start)
+                             return_lse=return_lse, doc_start=self.doc_start,
+                             softcap=self.softcap)
 
     def fwd(self, ext, q, k, v, scale):
+        if self.softcap is not None:
+            return ext.attn_cap_fwd(q, k, v, scale, self.mod, self.modarg, self.softcap)
         if self.doc_start is not None:
             return ext.attn_fwd_doc(q, k, v, scale, self.doc_start)
         return ext.attn_fwd(q, k, v, scale, self.mod, self.modarg, self.slopes)
 
     def bwd(self, ext, q, k, v, o, do, lse, scale, dq=None, dk=None, dv=None):
         """dq/dk/dv: out views to write in place; None or empty = allocate."""
+        if self.softcap is not None:
+            return ext.attn_cap_bwd(q, k, v, o, do, lse, scale, self.mod, self.modarg,
+                                    self.softcap, dq, dk, dv)
         if self.doc_start is not None:
             return ext.attn_bwd_doc(q, k, v, o, do, lse, scale, self.doc_start, self.doc_end,
                                     dq, dk, dv)
@@ -298,6 +321,7 @@ def flash_attention(
     alibi_slopes: Optional[torch.Tensor] = None,
     doc_start: Optional[torch.Tensor] = None,
     doc_end: Optional[torch.Tensor] = None,
+    softcap: Optional[float] = None,
 ) -> torch.Tensor:
     """Tiled attention, BSHD layout: [B,S,Hq,D] x [B,S,Hkv,D] -> [B,S,Hq,D]
     (q.shape[2] is the HEAD count — an int ``alibi_slopes`` relies on that).
@@ -323,10 +347,28 @@ def flash_attention(
         fault.
       * RoPE needs no per-document position reset: scores depend on
         q_pos - k_pos only.
+
+    Attention-logit soft-capping
+    ----------------------------
+    ``softcap=c`` (finite, > 0) bounds the scores: with ``x = scale * q.k``,
+    ``t = c * tanh(x / c)``, ``P = softmax(t)`` over the kept keys and the
+    saved log-sum-exp is that of ``t`` (Gemma-2 uses c = 50). The cap comes
+    after ``scale`` and before masking. The backward multiplies the score
+    gradient by ``1 - (t / c)^2``. On bf16 GPU inputs it runs the capped
+    instantiations of the same kernels (``attn_cap_fwd`` / ``attn_cap_bwd``:
+    one exp and one reciprocal more per score, nothing kept across a tile);
+    CPU and other dtypes run ``attention_ref(softcap=c)``.
+
+      * Masks: full, causal and sliding window. With ``doc_start``,
+        ``prefix_len`` or ALiBi it raises ``ValueError``: those masks have no
+        capped kernels yet, and a silent O(S^2) fallback in a training run is
+        worse than an error.
+      * It needs ``scale > 0``.
+      * ``softcap=None`` calls exactly the uncapped kernels.
     """
     B, Sq, Hq, _ = q.shape
     mask = _Mask.build(causal, window, prefix_len, alibi_slopes, doc_start, doc_end,
-                       B, Sq, k.shape[1], Hq, q.device)
+                       B, Sq, k.shape[1], Hq, q.device, softcap)
     return _FlashAttnFn.apply(q, k, v, scale, mask)
 
 
@@ -439,6 +481,7 @@ def rope_flash_attention_qkv(
     q_norm_weight: Optional[torch.Tensor] = None,
     k_norm_weight: Optional[torch.Tensor] = None,
     norm_eps: float = 1e-5,
+    softcap: Optional[float] = None,
 ) -> torch.Tensor:
     """qkv: [B, S, (Hq+2*Hkv)*D] fused projection output -> o [B, S, Hq, D].
 
@@ -448,14 +491,17 @@ def rope_flash_attention_qkv(
 
     ``q_norm_weight`` / ``k_norm_weight`` (``[head_dim]``, both or neither):
     per-head QK-norm before RoPE, see ``ops.qk_norm``. With both ``None`` the
-    path is the plain RoPE + attention one."""
+    path is the plain RoPE + attention one.
+
+    ``softcap``: attention-logit soft-capping, see ``flash_attention``; the
+    fused nodes stay one autograd node each and call the capped kernels."""
     from .qk_norm import HIP_HEAD_DIMS, qk_norm_rope
     from .rope import apply_rope
 
     B, S, _ = qkv.shape
     Hq, Hkv, D = n_heads, n_kv_heads, head_dim
     mask = _Mask.build(causal, window, prefix_len, alibi_slopes, doc_start, doc_end,
-                       B, S, S, Hq, qkv.device)
+                       B, S, S, Hq, qkv.device, softcap)
     if (q_norm_weight is None) != (k_norm_weight is None):
         raise ValueError("QK-norm needs both q_norm_weight and k_norm_weight")
     qk_norm = q_norm_weight is not None

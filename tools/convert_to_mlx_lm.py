@@ -87,6 +87,12 @@ def check_exportable(args: ModelArgs) -> None:
             "equivalent in the llama / qwen3 layouts this tool writes; the exported model "
             "would decode without the cap (a Gemma-2 layout is a ROADMAP item)"
         )
+    if getattr(args, "attn_logit_softcap", None):
+        raise NotImplementedError(
+            f"convert_to_mlx_lm: model.attention.logit_softcap = {args.attn_logit_softcap} "
+            "has no equivalent in the llama / qwen3 layouts this tool writes; the exported "
+            "model would attend with uncapped scores (a Gemma-2 layout is a ROADMAP item)"
+        )
 
 
 def hf_config_from(config: Config, args: ModelArgs) -> Dict:
